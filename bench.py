@@ -8,9 +8,13 @@ dynamic, so the same plan runs at 4096x4096).  One "step" = one evaluation of th
 function: one launch-list replay (a single host call into libaesara_hip.so) that issues the ONE
 fused Elemwise+Sum kernel (in-kernel deterministic finalize), with ``x`` resident in HBM.
 
-The same JSON line carries ``"secondary"``: every other BASELINE config at its full shape, each
-with its own ``roofline`` timed by HIP events in this run and a correctness assert against an
-fp64 restatement on the same data:
+A plain run (``--gpus 1 --steps K --warmup W``) does only that: set up, warm up, time K steps,
+print the line (``--dump-outputs DIR``: and write what the last timed step returned to
+``DIR/gauss_sum.npy``).  Everything else below runs with ``--full`` only.
+
+With ``--full`` the same JSON line carries ``"secondary"``: every other BASELINE config at its full
+shape, each with its own ``roofline`` timed by HIP events in this run and a correctness assert
+against an fp64 restatement on the same data:
 
 * cfg3b  Gemm fp32 4096^3 (the ``check_blas.py:54-57`` update ``C <- 0.4*C + 0.8*dot(A,B)``), MFMA-bound
 * cfg3a  Gemv fp64 4096^2 (``M.dot(v) + a``, BASELINE configs[2]'s graph), HBM-bound
@@ -29,7 +33,7 @@ MALL-cold figure; the same-buffer (cache-assisted) figure of earlier rounds ride
 ``config.warm``.  cfg3a does the same.
 
 Prints ONE JSON line (rank 0).  ``roofline`` is measured live with HIP events on the launch
-stream.  ``cpu_baseline`` (rank 0, N=1 only): the REFERENCE itself — its ``Mode("cvm","fast_run")``
+stream.  ``cpu_baseline`` (``--full``, rank 0, N=1 only): the REFERENCE itself — its ``Mode("cvm","fast_run")``
 C linker on this host (``oracle/time_reference.py`` in a child process, ``kind: "reference"``) when
 the reference front end is available (``/root/reference`` or the packed overlay ``oracle/_ref/``),
 else the oracle's C port of the same loops (``kind: "port"``).  With the front end available the
@@ -234,6 +238,12 @@ def main():
                     help="skip the untimed clock warm-up in front of the timed region")
     ap.add_argument("--rotate", type=int, default=8,
                     help="distinct input buffers the timed region cycles through (1 = same buffer)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the fp64 check of the benchmarked "
+                         "path, the sustained / same-buffer / executor-level / read-only-ceiling legs, "
+                         "the secondary configs and the CPU baseline with its reference comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
 
     import ctypes as C
@@ -335,11 +345,12 @@ def main():
         state["i"] = i + 1
         if world == 1:
             if fn is not None:
-                fn(xs[i % NROT])
+                state["last"] = fn(xs[i % NROT])
             else:
-                ex(xs[i % NROT], mu, sigma)
+                state["last"] = ex(xs[i % NROT], mu, sigma)[0]
             return None
         ex(xs[i % NROT], mu, sigma, out=[slots[i % R]])
+        state["last"] = slots[i % R]
         if (i + 1) % BUCKET == 0:
             lo = (i + 1 - BUCKET) % R
             _, hs = reducer(ring[lo:lo + BUCKET], async_op=True)
@@ -352,12 +363,13 @@ def main():
         torch.cuda.synchronize()
 
     # correctness of the benchmarked path against an fp64 restatement on the same data
-    for xk in (xs[0], xs[-1]):
-        (out,) = ex(xk, mu, sigma)
-        want = torch.exp(-(xk - 0.1) ** 2 / (2 * 1.3 ** 2)).sum()
-        rel = abs(out.item() - want.item()) / abs(want.item())
-        assert rel < 1e-9, f"benchmark result mismatch: rel err {rel}"
-    del want
+    if args.full:
+        for xk in (xs[0], xs[-1]):
+            (out,) = ex(xk, mu, sigma)
+            want = torch.exp(-(xk - 0.1) ** 2 / (2 * 1.3 ** 2)).sum()
+            rel = abs(out.item() - want.item()) / abs(want.item())
+            assert rel < 1e-9, f"benchmark result mismatch: rel err {rel}"
+        del want
 
     transport_error = None
     if world > 1 and comm_kind == "abi":
@@ -451,10 +463,19 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = elapsed.item()
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (a borrowed output buffer is overwritten by the legs
+        # below, so it is copied out now)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = torch.as_tensor(state["last"]).detach().to("cpu", torch.float64).numpy()
+        np.save(os.path.join(args.dump_outputs, "gauss_sum.npy"), last)
+
     # the driver's --steps may be small (20 evals = 0.55 ms): a longer untimed-by-contract run
     # of the same step gives the sustained figure next to it
     sustained = warm = through = exec_level = None
-    if world == 1:
+    if world == 1 and not args.full:
+        through = fn_info
+    elif world == 1:
         n_long = max(args.steps, 2000)
         state["i"] = 0
         d_ms, w_ms = timer.time(step, n_long, warmup=NROT)
@@ -493,7 +514,7 @@ def main():
     # what the hardware allows at this size with this launch shape: the same rotation through a
     # kernel that only loads and sums (no exp, no division) — the read-only ceiling of the headline
     ceiling = None
-    if world == 1:
+    if world == 1 and args.full:
         from aesara_amd.plan import Plan
         exs = PlanExecutor(Plan.from_json(SUM_PLAN), use_graph=G, borrow=True)
         (o,) = exs(xs[0])
@@ -512,7 +533,7 @@ def main():
                            "adds only (no ALU work to hide), in-kernel finalize included"}
         del exs
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # compiles the reference's C modules in the background while the secondary rows run — started
         # only now, behind every leg that is paced by host calls of a few microseconds: a few hundred
         # gcc processes next to the headline's 0.6 ms timed region cost it 4 us per eval (r04: 32.8 vs
@@ -521,7 +542,7 @@ def main():
         ref_warm = start_reference_warm()
 
     secondary = []
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         only = [s for s in args.only_secondary.split(",") if s]
         ctx = dict(torch=torch, np=np, dist=dist, timer=timer, plan_of=plan_of, randn=randn,
                    PlanExecutor=PlanExecutor, G=G, rank=rank, world=world, args=args,
@@ -634,7 +655,7 @@ def main():
             res["through_function"] = through    # top level: the driver's record keeps top-level keys
         if secondary:
             res["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(np, ref_warm, secondary)
             vs = res["cpu_baseline"].pop("vs_reference", None)
             if vs is not None:

@@ -93,6 +93,30 @@ def test_live_bench_line_meets_the_contract():
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_dumps_the_last_timed_output(tmp_path):
+    """A plain run (no --full) prints the headline line only, and ``--dump-outputs DIR`` writes
+    what the last timed step returned: the fp64 sum of config 2, the same in two runs."""
+    import numpy as np
+    vals = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12",
+                              "--warmup", "3", "--dump-outputs", str(d)], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 12 and line["warmup"] == 3
+        assert "secondary" not in line and "cpu_baseline" not in line
+        _check(line, need_cpu=False)
+        v = np.load(str(d / "gauss_sum.npy"))
+        assert v.dtype == np.float64 and v.shape == () and np.isfinite(v) and v > 0
+        vals.append(v)
+    assert vals[0] == vals[1]
+
+
+@pytest.mark.gpu
 def test_two_rank_bench_control_flow_on_one_device():
     """What the driver launches for N > 1 (`torch.distributed.run --nproc-per-node N bench.py
     --gpus N`), here with 2 ranks sharing cuda:0 over gloo (test hooks AESARA_BENCH_BACKEND /
@@ -108,7 +132,8 @@ def test_two_rank_bench_control_flow_on_one_device():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "8",
-                          "--cfg5-log2n", "20"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--full", "--cfg5-log2n", "20"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                         env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -142,7 +167,7 @@ def test_eight_rank_bench_control_flow_on_one_device():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "24", "--warmup", "8",
-                          "--cfg5-log2n", "20", "--only-secondary", "cfg5,placed", "--rotate", "2"],
+                          "--full", "--cfg5-log2n", "20", "--only-secondary", "cfg5,placed", "--rotate", "2"],
                          capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -10,7 +10,7 @@ set -u
 TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/profiles_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline"
+B="python $R/bench.py --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- $B --steps 2000 --warmup 50 --no-secondary > $O/bench_under_rocprof.json 2> $O/kt.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o bench -- $B --steps 200 --warmup 10 --no-secondary > /dev/null 2> $O/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -o bench -- $B --steps 200 --warmup 10 --no-secondary > /dev/null 2> $O/write.err

@@ -6,7 +6,7 @@ for l in sys.stdin:
     if l.startswith("{"):
         r=json.loads(l); c=r["config"]
         print("%-64s cold %.2f us (%.3f)  warm %.2f us (%.3f)" % (os.environ.get("TAG",""), c["sustained"]["kernel_ms"]*1e3, c["sustained"]["frac"], c["warm"]["kernel_ms"]*1e3, c["warm"]["frac"]))'
-run() { TAG="$*" env "$@" timeout 180 python bench.py --no-secondary --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | TAG="$*" python -c "$fmt"; }
+run() { TAG="$*" env "$@" timeout 180 python bench.py --full --no-secondary --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | TAG="$*" python -c "$fmt"; }
 run A=0
 run AESARA_HIP_NT=1
 run AESARA_HIP_RED_BPC=4
