@@ -4,7 +4,8 @@ Layers (bottom up):
 
 * ``csrc/``      hand-written HIP kernels + the C-ABI shim ``libaesara_hip.so`` (include/aesara_hip.h)
 * ``_lib``       ctypes binding of that C-ABI (fails loudly when the library is missing)
-* ``codegen``    HIP source generator for fused broadcast Elemwise(+CAReduce) kernels
+* ``codegen``    HIP source generators, one module per kernel family (fused Elemwise(+CAReduce), GEMV /
+  GEMM epilogues, row programs, row chains) on a shared prelude and scalar-expression emitter
 * ``executor``   runs a ``Plan`` on device arrays (PyTorch-ROCm tensors are only the container)
 * ``plan``       backend-neutral launch-plan IR (plain data, JSON)
 * ``lower`` / ``linker``  Aesara FunctionGraph -> Plan and the ``HipLinker(JITLinker)`` plug-in

@@ -76,19 +76,7 @@ class BlasMixin:
             waves = 4
         spec = cg.GemmEpiSpec(dt, nf, bkc, st.scalar, [o.dtype for o in others],
                               [o.dtype for o in outs], st.out_refs, waves=waves)
-        key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = cg.generate_gemm_epilogue(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run)
         g = GeArgs()
         g.M, g.N = M, N
         for d, (A, B) in enumerate(dots):

@@ -229,20 +229,9 @@ class ElemwiseMixin:
         mkey = (tuple(ext), L, V, nch, len(lsh), self.dry_run, long_rows, blk, big)
         hit = memo.get(mkey)
         if hit is None:
-            spec = cg.RowChainSpec(ext, spec_members, L, V, nch, lnd=len(lsh), block=blk, nt=big)
-            key = ("long-" if long_rows else "") + spec.key()
-            ent = _Kernels.cache.get(key) if not self.dry_run else \
-                ([None] if key in _Kernels.compiled else None)
-            if ent is None:
-                src, names = (cg.generate_rowchain_long if long_rows else cg.generate_rowchain)(spec)
-                if self.dry_run:
-                    from .device import compile_cached
-                    compile_cached(src)
-                    _Kernels.compiled[key] = 1
-                    ent = [None]
-                else:
-                    ent = load_kernels(src, names)
-                    _Kernels.cache[key] = ent
+            spec = cg.RowChainSpec(ext, spec_members, L, V, nch, lnd=len(lsh), block=blk, nt=big,
+                                   long_rows=long_rows)
+            ent = _Kernels.get(spec, load=not self.dry_run)
             hit = memo[mkey] = (ent, spec.block)
         ent, block = hit
         g = RcArgs()
@@ -300,19 +289,7 @@ class ElemwiseMixin:
             g.stride[k] = 0 if (o.shape[0] == 1 and N != 1) else o.strides[0]
         g.col_ws, g.red_ws = col_ws.ptr, red_ws.ptr
         g.nops, g.nred = len(allops), nred
-        key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = cg.generate_rowpass(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run)
         waves = spec.block // 64
         shmem = waves * K * ITEMSIZE[dt] + waves * 8 * 8
         self._launch("ahip_rowpass", (ent[0], C.byref(g), spec.block, rpw, shmem, self._stream()))
@@ -379,7 +356,7 @@ class ElemwiseMixin:
 
     @staticmethod
     def _tile_plan(cshape, cstrides, nin, dtypes):
-        """Layout test for the LDS-tiled Elemwise kernel (codegen.generate_tiled): some input has
+        """Layout test for the LDS-tiled Elemwise kernel (codegen.elemwise.generate_tiled): some input has
         its unit stride along a dim other than the last one (a transposing DimShuffle view) while
         every output is contiguous along the last dim.  Returns (tile_dim, tile, classes) or
         None."""
@@ -563,19 +540,7 @@ class ElemwiseMixin:
         spec = cg.GemvEpiSpec(dt, dot_vec, st.scalar, [o.dtype for o in others],
                               [o.dtype for o in outs], st.out_refs, rpw=rpw, kvs=kvs,
                               xprogs=xprogs, nt=big or bool(TUNE["nt"] & 1))
-        key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = cg.generate_gemv_epilogue(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run)
         g.M = M
         self._launch("ahip_gemv_epilogue", (ent[0], C.byref(g), spec.block * 1, self._stream()))
 

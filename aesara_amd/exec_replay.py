@@ -558,7 +558,7 @@ class ReplayMixin:
 
     def _reduce_err(self):
         """int32 view of the device error word of the in-kernel reduce finalize
-        (codegen.REDUCE_ERR_OFF): the epoch of the last launch that timed out, 0 if none ever did"""
+        (codegen.finalize.REDUCE_ERR_OFF): the epoch of the last launch that timed out, 0 if none ever did"""
         off = lib.ahip_reduce_partials_bytes() + 2048 + cg.REDUCE_ERR_OFF
         return self._ws[off:off + 4].view(torch.int32)
 

@@ -452,18 +452,7 @@ class ScanMixin:
         R, nw, G, place = geo
         spec = sp.Spec(prog, lp, M, Ks, lens, R, nw, place, dtype=f32)
         key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = sp.generate(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run, key=key)
         # nit-sot buffers (the host loop allocates them after its first step)
         for k, v in prog.passthru.items():
             src = seqs[prog.seq[v]] if prog.seq[v] < n_seqs else pre_rows[prog.seq[v] - n_seqs]
@@ -774,18 +763,7 @@ class ScanMixin:
                 if v not in seq_arr and v not in nsq and v not in folded:
                     return "operand of unknown layout"
         key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = sm.generate(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run, key=key)
         for k, v in prog.passthru.items():
             src = seqs[prog.seq[v]] if prog.seq[v] < n_seqs else pre_rows[prog.seq[v] - n_seqs]
             if store[k] != n_steps or src.ndim != 3 or tuple(src.shape[1:]) != (Bn, Nt) or src.dtype != f32:
@@ -994,19 +972,7 @@ class ScanMixin:
             sh_vals.append(inner.contiguous(x))
             sh_dt.append(x.dtype)
         spec = se.SpecEw(prog, lp, out_dt, sh_dt, bc)
-        key = spec.key()
-        ent = _Kernels.cache.get(key) if not self.dry_run else \
-            ([None] if key in _Kernels.compiled else None)
-        if ent is None:
-            src, names = se.generate(spec)
-            if self.dry_run:
-                from .device import compile_cached
-                compile_cached(src)
-                _Kernels.compiled[key] = 1
-                ent = [None]
-            else:
-                ent = load_kernels(src, names)
-                _Kernels.cache[key] = ent
+        ent = _Kernels.get(spec, load=not self.dry_run)
         for j in range(n_nit):
             sl = n_mm + n_rec + j
             outs[sl] = inner.alloc((store[sl],) + tuple(nit_shape[j]), out_dt[sl])

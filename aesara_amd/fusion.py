@@ -1878,7 +1878,7 @@ def _fuse_rowchain(plan: Plan, steps: List[Step], max_ops: int = 16) -> List[Ste
     """A last-axis CAReduce whose (keepdims) result feeds Elemwise / further last-axis CAReduce
     steps over the same [..., K] space (softmax = max -> exp-sum -> scale; log-softmax; softmax
     gradient; mean/variance normalisation) becomes ONE "rowchain" step: every operand is read
-    once, every intermediate between the reductions lives in registers (codegen.RowChainSpec).
+    once, every intermediate between the reductions lives in registers (codegen.rowchain.RowChainSpec).
     The reference runs such chains as separate passes (Softmax.c_code tensor/special.py:372-415)
     or separate nodes.  Run-time layout checks are the executor's; the original steps are kept
     as the fallback."""

@@ -35,7 +35,7 @@ _def("FASTDIV", 2, int, "x / c for a loop-invariant RUN-TIME c (a broadcast scal
      "reciprocal + Markstein step: the correctly rounded IEEE quotient, what the reference computes; 1 = always "
      "x * (1/c), <= 1.5 ulp from the quotient (exact quotients such as 21/7 are then inexact: floor / eq / int casts "
      "downstream can differ — opt-in only); 2 (default) = x * (1/c) ONLY for a quotient that reaches memory solely as a "
-     "term of the kernel's own floating-point sum through continuous functions (codegen.sum_only_nodes: a result that "
+     "term of the kernel's own floating-point sum through continuous functions (codegen.scalar.sum_only_nodes: a result that "
      "already depends on the order of summation), IEEE everywhere else — any quotient that is stored, compared, rounded "
      "or cast is exact.  Config 2 (r06, one box): 26.9 us per eval with 0, 24.8 with 1 / 2")
 _def("RC_NT", None, int, "row chains: non-temporal loads of the full operands (default: operands of 96 MiB or more; "

@@ -477,6 +477,9 @@ class Spec:
                           sort_keys=True)
         return hashlib.sha256(blob.encode()).hexdigest()[:24]
 
+    def generate(self):
+        return generate(self)
+
 
 def xch_layout(prog, lens, gpv=1):
     """granule offsets of the exchange buffer: per exchanged vector 4 slots of padded length
@@ -814,7 +817,7 @@ def generate(spec: Spec):
         L.extend(lines)
         pub = list(zip(ph["outs"], ph["out_refs"])) + ([(red["u"], red["ref"])] if red else [])
         for k, (o, ri) in enumerate(pub):
-            L.append("      own_%d = %s;" % (o, cg._cast(outs[ri], odts[ri], spec.dtype)))
+            L.append("      own_%d = %s;" % (o, cg.cast(outs[ri], odts[ri], spec.dtype)))
             if o in pr.zero_d:
                 # a 0-d result (every lane holds it): one lane of workgroup 0 stores it
                 for kind, j in out_of.get(o, []):

@@ -289,6 +289,9 @@ class SpecEw:
             blob += ["wg1", sorted(pr.cls.items()), [s.get("reduce") for s in pr.steps]]
         return hashlib.sha256(json.dumps(blob, sort_keys=True).encode()).hexdigest()[:24]
 
+    def generate(self):
+        return generate(self)
+
 
 def slot_kinds(pr: ProgramEw):
     """(kinds of the recurrent outputs, of the nit-sot outputs, of the shared values): 1 = one
@@ -429,7 +432,7 @@ def generate(spec: SpecEw):
             L.extend(lines)
             for o, ri_ in zip(st["outs"], st["out_refs"]):
                 nm = "v%d_u%d" % (o, u)
-                L.append("      const %s %s = %s;" % (RT[dt[o]], nm, cg._cast(outs[ri_], odts[ri_], dt[o])))
+                L.append("      const %s %s = %s;" % (RT[dt[o]], nm, cg.cast(outs[ri_], odts[ri_], dt[o])))
                 env[o] = nm
             red = st.get("reduce")
             if red is not None:
@@ -440,7 +443,7 @@ def generate(spec: SpecEw):
                 comb = lambda a_, b_, _r=red: cg.red_combine(_r["op"], _r["acc"], a_, b_)  # noqa: E731
                 rv = "rd%d_u%d" % (si, u)
                 L.append("      %s %s = live ? %s : %s;" % (
-                    acc_t, rv, cg._cast(outs[red["ref"]], odts[red["ref"]], red["acc"]),
+                    acc_t, rv, cg.cast(outs[red["ref"]], odts[red["ref"]], red["acc"]),
                     "(%s)%s" % (acc_t, cg.red_identity(red["op"], red["acc"]))))
                 L.extend(cg.wave_fold_lines(acc_t, comb, var=rv, indent="      "))
                 L.append("      if (nw_ > 1u) {")
@@ -451,21 +454,21 @@ def generate(spec: SpecEw):
                     rv, comb(rv, "(%s)smr%d[t & 1][w_]" % (acc_t, ri))))
                 L.append("      }")
                 nm = "v%d_u%d" % (red["out"], u)
-                L.append("      const %s %s = %s;" % (RT[dt[red["out"]]], nm, cg._cast(rv, red["acc"], dt[red["out"]])))
+                L.append("      const %s %s = %s;" % (RT[dt[red["out"]]], nm, cg.cast(rv, red["acc"], dt[red["out"]])))
                 env[red["out"]] = nm
                 ri += 1
 
         def st_val(v, odt):
-            e_ = cg._cast(env[v], dt[v], odt)
+            e_ = cg.cast(env[v], dt[v], odt)
             return "(unsigned char)(%s)" % e_ if odt == "bool" else e_
         # every new value is taken before any register of the step's inputs is overwritten
         for g_ in range(n_mm):
             odt = spec.out_dtypes[g_]
             for tap, v in pr.mm_new[g_]:
-                L.append("      const %s nm%d_%d = %s;" % (RT[odt], g_, tap, cg._cast(env[v], dt[v], odt)))
+                L.append("      const %s nm%d_%d = %s;" % (RT[odt], g_, tap, cg.cast(env[v], dt[v], odt)))
         for k in range(n_rec):
             odt = spec.out_dtypes[n_mm + k]
-            L.append("      const %s n%d = %s;" % (RT[odt], k, cg._cast(env[pr.rec_new[k]], dt[pr.rec_new[k]], odt)))
+            L.append("      const %s n%d = %s;" % (RT[odt], k, cg.cast(env[pr.rec_new[k]], dt[pr.rec_new[k]], odt)))
         for g_ in range(n_mm):
             odt = spec.out_dtypes[g_]
             for tap, v in pr.mm_new[g_]:
@@ -485,10 +488,10 @@ def generate(spec: SpecEw):
                 st_val(pr.nit_new[j], spec.out_dtypes[sl])))
         sh_tmp = []
         for m, v in enumerate(pr.sh_new):
-            L.append("      const %s ns%d = %s;" % (RT[spec.sh_dtypes[m]], m, cg._cast(env[v], dt[v], spec.sh_dtypes[m])))
+            L.append("      const %s ns%d = %s;" % (RT[spec.sh_dtypes[m]], m, cg.cast(env[v], dt[v], spec.sh_dtypes[m])))
             sh_tmp.append(m)
         if pr.cond is not None:
-            L.append("      const bool stop_ = (bool)(%s);" % cg._cast(env[pr.cond], dt[pr.cond], "bool"))
+            L.append("      const bool stop_ = (bool)(%s);" % cg.cast(env[pr.cond], dt[pr.cond], "bool"))
         # shift the taps, advance the circular positions
         for k in range(n_rec):
             for d in range(pr.depth[k], 1, -1):

@@ -191,6 +191,9 @@ class SpecMat:
                           sort_keys=True)
         return hashlib.sha256(blob.encode()).hexdigest()[:24]
 
+    def generate(self):
+        return generate(self)
+
 
 def xfold_pairs(prog, lifted_outs):
     """In-kernel sequence products (round 3).  ``lifted_outs``: loop-plan variables that are rows of
@@ -645,7 +648,7 @@ def generate(spec: SpecMat):
                                                 indent="      ", suffix="_p%d" % pi)
         L.extend(lines)
         for o, ri in zip(ph["outs"], ph["out_refs"]):
-            L.append("      own_%d = %s;" % (o, cg._cast(outs[ri], odts[ri], "float32")))
+            L.append("      own_%d = %s;" % (o, cg.cast(outs[ri], odts[ri], "float32")))
             if o in xoff and not FLAG:
                 xo, lp = xoff[o]
                 L.append("      __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + erow * %d + en, "
@@ -1451,7 +1454,7 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
                                                 indent="      ", suffix="_p%d" % pi)
         L.extend(lines)
         for o, ri in zip(ph["outs"], ph["out_refs"]):
-            L.append("      own_%d§ = %s;" % (o, cg._cast(outs[ri], odts[ri], spec.dtype)))
+            L.append("      own_%d§ = %s;" % (o, cg.cast(outs[ri], odts[ri], spec.dtype)))
         L.append("    }")
         # publish first (the hand-off is the critical path), the stores into the output buffers after
         pending_pub.extend(o for o in ph["outs"] if o in xoff)

@@ -58,7 +58,7 @@ enum ahip_red_op { AHIP_RED_SUM = 0, AHIP_RED_PROD = 1, AHIP_RED_MAX = 2, AHIP_R
 
 /* Kernel-argument block of every GENERATED fused Elemwise(+CAReduce) kernel
  *   extern "C" __global__ void k(ahip_ew_args a);
- * (generator: aesara_amd/codegen.py).  Operands are ordered inputs then outputs.            */
+ * (generator: aesara_amd/codegen/elemwise.py).  Operands are ordered inputs then outputs.   */
 typedef struct ahip_ew_args {
   int64_t n;                              /* total number of output elements (kept x reduced) */
   int64_t shape[AHIP_MAXD];               /* collapsed iteration shape, outermost first       */
@@ -76,7 +76,7 @@ typedef struct ahip_ew_args {
  * kernel: up to AHIP_HJOBS independent jobs of ONE kernel specialisation (same scalar program,
  * dtypes, flat contiguous operands) — each job its own operands, length and result — share one
  * grid: workgroups [wg0[j], wg0[j + 1]) belong to job j.
- *   extern "C" __global__ void k(ahip_ewh_args h);      (codegen.generate, spec.hjobs)        */
+ *   extern "C" __global__ void k(ahip_ewh_args h);      (codegen.elemwise, spec.hjobs)        */
 #define AHIP_HJOBS 16
 #define AHIP_HOPS 6
 typedef struct ahip_ewh_args {
@@ -90,7 +90,7 @@ typedef struct ahip_ewh_args {
 } ahip_ewh_args;
 
 /* Kernel-argument block of the GENERATED fused GEMV-chain + Elemwise epilogue kernels
- *   extern "C" __global__ void k(ahip_gv_args a);       (codegen.generate_gemv_epilogue)
+ *   extern "C" __global__ void k(ahip_gv_args a);       (codegen.gemv_epi)
  * y[m] = f(dot_0[m], .., dot_{D-1}[m], operands[m]),  dot_d[m] = sum_k A_d[m*a_rs + k*a_cs] * x_d[k*incx] */
 #define AHIP_MAXDOTS 8
 #define AHIP_GV_MAXOPS 16
@@ -110,7 +110,7 @@ typedef struct ahip_gv_args {
 } ahip_gv_args;
 
 /* Kernel-argument block of the GENERATED single-pass "row program" kernels
- *   extern "C" __global__ void k(ahip_rp_args a);       (codegen.generate_rowpass)
+ *   extern "C" __global__ void k(ahip_rp_args a);       (codegen.rowpass)
  * per row m of the row-major N x K matrix X: d = X[m,:].w, a scalar program over d and the
  * row-wise operands, Sum partials of some of its values, and the column accumulation
  * g[k] += X[m,k] * r[m]; one partial per workgroup goes to col_ws [grid][K] / red_ws [grid][nred]. */
@@ -124,7 +124,7 @@ typedef struct ahip_rp_args {
 } ahip_rp_args;
 
 /* Kernel-argument block of the GENERATED "row-chain" kernels
- *   extern "C" __global__ void k(ahip_rc_args a);       (codegen.generate_rowchain)
+ *   extern "C" __global__ void k(ahip_rc_args a);       (codegen.rowchain)
  * rows of a [lshape..., K] space (K contiguous, N = prod(lshape) rows, up to 4 jointly-collapsed
  * leading dims); ptr: external operands then stored outputs; ls[k][d] = element stride of operand k
  * along leading dim d (0 = broadcast).                                                          */
@@ -138,7 +138,7 @@ typedef struct ahip_rc_args {
 } ahip_rc_args;
 
 /* Kernel-argument block of the GENERATED small-M "GEMM chain + epilogue" kernels
- *   extern "C" __global__ void k(ahip_ge_args a);       (codegen.generate_gemm_epilogue)
+ *   extern "C" __global__ void k(ahip_ge_args a);       (codegen.gemm_epi)
  * out[m,n] = f(A_0 @ B_0, ..., operands[m,n]); A_d is [M, K_d] k-contiguous (row stride a_rs),
  * B_d is [K_d, N] with element strides (b_rs, b_cs); ptr/rs/cs: epilogue operands then outputs
  * (element strides along m / n, 0 = broadcast).                                                 */

@@ -1,4 +1,4 @@
-"""The hand-written float64 ``exp`` (``exp_tbl64``, aesara_amd/codegen.py) on the device, against
+"""The hand-written float64 ``exp`` (``exp_tbl64``, aesara_amd/codegen/prelude.py) on the device, against
 the reference's ``Exp.c_code`` (scalar/basic.py:3102: the C library's ``exp``) run through the
 reference's own C linker, and against NumPy: the edges of the range (|x| >= 708 takes the rare
 branch: clamp + ``v_ldexp_f64``), the denormal results (-745.13 .. -708.4), overflow / underflow,
@@ -83,7 +83,7 @@ def _device_exp(x, nd=1):
 def test_exp_tbl64_is_the_kernel_under_test(monkeypatch):
     """The float64 ``exp`` kernels these tests launch really are generated with the table form."""
     import torch
-    from aesara_amd import exec_common, exec_elemwise, knobs
+    from aesara_amd import exec_common, knobs
     from aesara_amd.executor import PlanExecutor
     assert int(knobs.get("FASTEXP")) == 1
     seen = []
@@ -92,8 +92,7 @@ def test_exp_tbl64_is_the_kernel_under_test(monkeypatch):
     def spy(src, names):
         seen.append(src)
         return real(src, names)
-    monkeypatch.setattr(exec_common, "load_kernels", spy)       # _Kernels.get (flat / n-d kernels)
-    monkeypatch.setattr(exec_elemwise, "load_kernels", spy)     # row chains, tiled forms
+    monkeypatch.setattr(exec_common, "load_kernels", spy)       # _Kernels.get: every kernel family
     exec_common._Kernels.cache.clear()                          # (kernels other tests already loaded)
     for nd, shape in ((1, (4099,)), (2, (37, 1000))):
         PlanExecutor(_exp_plan(nd))(torch.zeros(shape, dtype=torch.float64, device="cuda"))

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Constants of codegen.py's table-driven float64 exp (exp_tbl64): 2^(j/64) correctly rounded,
+"""Constants of codegen/prelude.py's table-driven float64 exp (exp_tbl64): 2^(j/64) correctly rounded,
 ln2/64 split for an exact k*C1, and the degree-3 near-minimax polynomial of
 (e^r - 1 - r) / r^2 on |r| <= ln2/128 (interpolation at Chebyshev nodes, 60-digit arithmetic).
-Prints C++ hex-float literals; codegen.py carries the output verbatim."""
+Prints C++ hex-float literals; codegen/prelude.py carries the output verbatim."""
 from decimal import Decimal, getcontext
 from fractions import Fraction
 import math
