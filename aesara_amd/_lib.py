@@ -173,6 +173,11 @@ SIGNATURES = {
     "ahip_arange": (i32, [i32, vp, vp, i64, vp, vp]),
     "ahip_cumulative_ws_bytes": (sz, [i32, i64, i64, i64]),
     "ahip_cumulative": (i32, [i32, i32, vp, i64, i64, i64, i64, i64, i64, vp, vp, sz, vp]),
+    "ahip_fft_ws_bytes": (sz, [i32, i64]),
+    "ahip_fft_r2c": (i32, [i32, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, sz, vp]),
+    "ahip_fft_c2c": (i32, [i32, i32, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, sz,
+                           vp]),
+    "ahip_fft_c2r": (i32, [i32, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, sz, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

@@ -1,6 +1,7 @@
-"""Shape, allocation, indexing, sorting and cumulative Ops of a PlanExecutor (views on the host,
-csrc/copy.hip / index.hip / sort.hip / cumulative.hip kernels; reference: tensor/basic.py,
-tensor/subtensor.py, tensor/shape.py, tensor/sort.py, tensor/extra_ops.py).
+"""Shape, allocation, indexing, sorting, cumulative and Fourier Ops of a PlanExecutor (views on the
+host, csrc/copy.hip / index.hip / sort.hip / cumulative.hip / fft.hip kernels; reference:
+tensor/basic.py, tensor/subtensor.py, tensor/shape.py, tensor/sort.py, tensor/extra_ops.py,
+tensor/fft.py).
 
 Part of :class:`aesara_amd.executor.PlanExecutor` (a mixin: the methods run on the executor's
 state; split out of executor.py in round 4, no behaviour change)."""
@@ -159,6 +160,17 @@ class OpsMixin:
         return self.materialize(x)
 
     def _op_IncSubtensor(self, node, args):
+        if isinstance(args[0], np.ndarray) and args[0].ndim == 1 and args[0].dtype.kind in "iu" \
+                and isinstance(args[1], (np.ndarray, np.generic)) and np.asarray(args[1]).dtype.kind in "iu":
+            # an integer vector built on the host (MakeVector of Shape_i: the ``s`` that
+            # tensor/fft.py:89,202 derives with set_subtensor): shape arithmetic, stays on the host
+            index = hostops.resolve_index(node.params["idx_list"], [self.host_int(a) for a in args[2:]])
+            out = np.array(args[0], copy=True)
+            if node.params["set_instead_of_inc"]:
+                out[index] = args[1]
+            else:
+                out[index] += np.asarray(args[1]).astype(out.dtype)
+            return [out]
         x, y = self.to_device(args[0]), self.to_device(args[1])
         index = hostops.resolve_index(node.params["idx_list"], [self.host_int(a) for a in args[2:]])
         out = self._own_or_copy(node.inputs[0], x)
@@ -813,6 +825,89 @@ class OpsMixin:
                                              _VP(ws.ptr) if ws is not None else None, need,
                                              self._stream()))
         return [out]
+
+    # ------------------------------------------------------------------ FFT ----------
+    FFT_MAX_POW2, FFT_MAX_OTHER = 4096, 2048      # csrc/fft.hip: one transform per workgroup's LDS
+
+    def _fft_axis(self, kind, x, axis, n, inverse=False):
+        """One pass of csrc/fft.hip along ``axis``: ``r2c`` (real in, bins 0 .. n/2 out), ``c2c`` or
+        ``c2r`` (bins 0 .. n/2 in, n reals out, unnormalised).  Complex arrays carry a trailing
+        dimension of 2.  The axis is cropped / zero-padded to ``n`` (NumPy's ``s``); the input is
+        read through its strides when the dims in front of and behind the axis each collapse to
+        one stride, and copied otherwise.  Returns a fresh C-contiguous array."""
+        cin, cout = kind != "r2c", kind != "c2r"
+        dt = x.dtype
+        if n < 1:
+            raise ValueError(f"Invalid number of FFT data points ({n}) specified.")
+        need = int(lib.ahip_fft_ws_bytes(dtype_code(dt), n))
+        if need == 0:
+            raise NotImplementedError(
+                f"FFT along an axis of length {n}: the device transform takes powers of two up to "
+                f"{self.FFT_MAX_POW2} and other lengths up to {self.FFT_MAX_OTHER}")
+        if cin and x.shape[-1] == 2 and x.strides[-1] != 1:
+            x = self.materialize(x)
+        end = x.ndim - 1 if cin else x.ndim
+        lead, tail = list(x.shape[:axis]), list(x.shape[axis + 1:end])
+        nout = n // 2 + 1 if kind == "r2c" else n
+        out = self.alloc(lead + [nout] + tail + ([2] if cout else []), dt)
+        if out.size == 0:
+            return out
+        osh, ost = collapse_dims(lead or [1], [list(x.strides[:axis]) or [0]])
+        ish, ist = collapse_dims(tail or [1], [list(x.strides[axis + 1:end]) or [0]])
+        if len(osh) != 1 or len(ish) != 1:
+            x = self.materialize(x)
+            osh, ost = collapse_dims(lead or [1], [list(x.strides[:axis]) or [0]])
+            ish, ist = collapse_dims(tail or [1], [list(x.strides[axis + 1:end]) or [0]])
+        outer, inner = _prod(lead), _prod(tail)
+        valid = min(x.shape[axis], n // 2 + 1 if kind == "c2r" else n)
+        o_si = 2 if cout else 1
+        o_sn = inner * o_si
+        ws = self.alloc((need,), "uint8")
+        head = (dtype_code(dt),) + ((1 if inverse else 0,) if kind == "c2c" else ())
+        self._launch("ahip_fft_" + kind, head + (
+            _VP(x.ptr), outer, n, inner, valid, ost[0][0], x.strides[axis], ist[0][0],
+            _VP(out.ptr), nout * o_sn, o_sn, o_si, _VP(ws.ptr), need, self._stream()))
+        return out
+
+    def _fft_operands(self, node, args, complex_in):
+        a = self.to_device(args[0])
+        s = [int(v) for v in self.host_array(args[1]).reshape(-1)]
+        dt = self.plan.vars[node.outputs[0]].dtype
+        if a.dtype != dt or dt not in ("float32", "float64"):
+            raise TypeError(f"{node.op}: {a.dtype} input (float32 / float64 only)")
+        nd = a.ndim - 1 - (1 if complex_in else 0)       # transformed axes: 1 .. nd
+        if complex_in and a.shape[-1] != 2:
+            raise ValueError(f"{node.op}: the last dimension holds (re, im) pairs, got {a.shape[-1]}")
+        if len(s) != nd:                               # np.fft._raw_fftnd / _cook_nd_args
+            raise ValueError("Shape and axes have different lengths.")
+        for n in s:
+            if n < 1:
+                raise ValueError(f"Invalid number of FFT data points ({n}) specified.")
+        return a, s, nd
+
+    def _op_RFFT(self, node, args):
+        """reference: tensor/fft.py:39 RFFTOp.perform — ``np.fft.rfftn(a, s)`` over all axes but
+        the first, (re, im) in a new last dimension: real -> complex on the last axis, then
+        complex transforms along the others, last to first (np.fft.rfftn's order)."""
+        a, s, nd = self._fft_operands(node, args, False)
+        # rows beyond s along the axes still to come are never read: drop them from the first pass
+        shape = [a.shape[0]] + [min(a.shape[d], s[d - 1]) for d in range(1, nd)] + [a.shape[nd]]
+        x = self._fft_axis("r2c", a.view(shape, a.strides), nd, s[-1])
+        for d in range(nd - 1, 0, -1):
+            x = self._fft_axis("c2c", x, d, s[d - 1])
+        return [x]
+
+    def _op_IRFFT(self, node, args):
+        """reference: tensor/fft.py:100 IRFFTOp.perform — ``np.fft.irfftn(a, s) * prod(s)``: the
+        unnormalised inverse; complex inverses along the leading axes first, complex -> real on
+        the last axis last (np.fft.irfftn's order)."""
+        a, s, nd = self._fft_operands(node, args, True)
+        shape = [a.shape[0]] + [min(a.shape[d], s[d - 1]) for d in range(1, nd)] \
+            + [min(a.shape[nd], s[-1] // 2 + 1), 2]
+        x = a.view(shape, a.strides)
+        for d in range(1, nd):
+            x = self._fft_axis("c2c", x, d, s[d - 1], inverse=True)
+        return [self._fft_axis("c2r", x, nd, s[-1])]
 
     def _op_AdvancedSubtensor1(self, node, args):
         x, idx = self.to_device(args[0]), self.to_device(args[1])

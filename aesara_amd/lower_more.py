@@ -2,7 +2,8 @@
 each DECOMPOSED into plan primitives that already have HIP kernels (Elemwise / CAReduce /
 Subtensor / AdvancedSubtensor / CumOp / Sort / Nonzero / Join ...) plus two new primitives:
 ``Searchsorted`` (csrc/index.hip, one binary search per element) and ``HostCall`` (an Op whose
-DEFINITION is a Python callable: ``Print``'s print function, ``as_op`` functions).
+DEFINITION is a Python callable: ``Print``'s print function, ``as_op`` functions).  ``RFFTOp`` /
+``IRFFTOp`` map one to one onto the plan ops ``RFFT`` / ``IRFFT`` (csrc/fft.hip).
 
 Registered by ``lower._register_handlers``; every handler cites the reference Op it restates.
 """
@@ -505,6 +506,28 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
             grids = [b.grid(lead[d], d, nd) for d in range(nd - 1)]
             out = b.adv_set(empty, xv, grids + [yv])
         ctx.vmap[node.outputs[0]] = out
+
+    # ---------------------------------------------------------------------------------------
+    from aesara.tensor.fft import IRFFTOp, RFFTOp
+
+    def _fft(opname, node, ctx, nd_out):
+        a, s = node.inputs
+        dt = str(a.type.dtype)
+        if dt not in ("float32", "float64"):
+            raise UnsupportedOp(f"{type(node.op).__name__} over dtype {dt} (float32 / float64 only)")
+        ctx.vmap[node.outputs[0]] = ctx.raw(opname, [ctx.vid(a), ctx.vid(s)], dt, [None] * nd_out)
+
+    @hip_lower.register(RFFTOp)
+    def _(op, node, ctx):
+        # reference: tensor/fft.py:12 RFFTOp (perform :39: np.fft.rfftn(a, s) over all axes but the
+        # first, (re, im) in a new last dimension) -> csrc/fft.hip, one pass per axis
+        _fft("RFFT", node, ctx, node.inputs[0].type.ndim + 1)
+
+    @hip_lower.register(IRFFTOp)
+    def _(op, node, ctx):
+        # reference: tensor/fft.py:72 IRFFTOp (perform :100: np.fft.irfftn(a, s) * prod(s), the
+        # unnormalised inverse of the above)
+        _fft("IRFFT", node, ctx, node.inputs[0].type.ndim - 1)
 
     # ---------------------------------------------------------------------------------------
     from aesara.tensor.sort import TopKOp

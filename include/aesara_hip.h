@@ -445,6 +445,30 @@ size_t ahip_cumulative_ws_bytes(int dtype, int64_t outer, int64_t n, int64_t inn
 int ahip_cumulative(int dtype, int mul, const void* x, int64_t outer, int64_t n, int64_t inner,
                     int64_t x_so, int64_t x_sn, int64_t x_si, void* out, void* ws,
                     size_t ws_bytes, void* stream);
+/* ---- K14: one-axis Fourier transforms (real -> complex, complex <-> complex, complex -> real) --
+ * replaces: tensor/fft.py:39 RFFTOp.perform (np.fft.rfftn) and :100 IRFFTOp.perform (np.fft.irfftn
+ * times prod(s)): one call per transformed axis.  Complex values are interleaved (re, im) pairs of
+ * `dtype` (float32 / float64).  The problem is [outer, n, inner]; strides count real scalars, for
+ * the input and for the output.  `valid`: entries of the input axis that exist — the rest of the
+ * length-n transform reads as zero, longer input is cropped (the whole of `s` handling).
+ *   r2c: real input, writes bins 0 .. n/2;
+ *   c2c: forward (inverse = 0) or unnormalised inverse;
+ *   c2r: reads bins 0 .. n/2 (Im of bin 0 and, for even n, of bin n/2 ignored), writes n reals,
+ *        unnormalised.
+ * n < 1: AHIP_EINVAL with NumPy's text.  Powers of two up to 4096 and other lengths (Bluestein) up
+ * to 2048 run in one workgroup's LDS; longer axes: AHIP_ENOSUP.  Twiddles, chirp and chirp spectrum
+ * are rebuilt per call in the caller-provided workspace of ahip_fft_ws_bytes(dtype, n) bytes
+ * (0 = unsupported length or dtype); nothing is allocated, every launch is recordable.            */
+size_t ahip_fft_ws_bytes(int dtype, int64_t n);
+int ahip_fft_r2c(int dtype, const void* x, int64_t outer, int64_t n, int64_t inner, int64_t valid,
+                 int64_t x_so, int64_t x_sn, int64_t x_si, void* out, int64_t o_so, int64_t o_sn,
+                 int64_t o_si, void* ws, size_t ws_bytes, void* stream);
+int ahip_fft_c2c(int dtype, int inverse, const void* x, int64_t outer, int64_t n, int64_t inner,
+                 int64_t valid, int64_t x_so, int64_t x_sn, int64_t x_si, void* out, int64_t o_so,
+                 int64_t o_sn, int64_t o_si, void* ws, size_t ws_bytes, void* stream);
+int ahip_fft_c2r(int dtype, const void* x, int64_t outer, int64_t n, int64_t inner, int64_t valid,
+                 int64_t x_so, int64_t x_sn, int64_t x_si, void* out, int64_t o_so, int64_t o_sn,
+                 int64_t o_si, void* ws, size_t ws_bytes, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
