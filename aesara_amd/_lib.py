@@ -178,6 +178,10 @@ SIGNATURES = {
     "ahip_fft_c2c": (i32, [i32, i32, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, sz,
                            vp]),
     "ahip_fft_c2r": (i32, [i32, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, sz, vp]),
+    "ahip_im2col2d": (i32, [i32, vp, p_i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64,
+                            i64, vp, vp]),
+    "ahip_col2im2d": (i32, [i32, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64,
+                            vp, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

@@ -70,7 +70,7 @@ _RED_OPS = {"add": "add", "maximum": "maximum", "minimum": "minimum"}
 _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   "AdvancedSubtensor", "AdvancedIncSubtensor", "Reshape", "Join", "Split",
                   "CumOp", "Argmax", "MaxAndArgmax", "Sort", "ArgSort", "IfElse", "BatchedDot",
-                  "MatMul", "Ger", "RFFT", "IRFFT"}
+                  "MatMul", "Ger", "RFFT", "IRFFT", "Conv2d", "Conv2dGradW", "Conv2dGradI"}
 
 
 def _const_scalar(plan: Plan, vid: int):

@@ -60,6 +60,9 @@ _def("COPY_STREAM_BYTES", None, int, "strided copies of at least this many bytes
 _def("GEMM_HALF_KSPLIT", None, int, "K groups inside a 64x64-tile workgroup (default: 4 up to one workgroup per CU, "
      "2 up to two, else 1; 1 / 2 / 4 forces it)")
 _def("GE_WAVES", 0, int, "waves per workgroup of the generated GEMM epilogue (0: automatic)")
+# ---- convolution ---------------------------------------------------------------------------------
+_def("CONV_WS_MB", 256, float, "MiB of im2col workspace of a convolution (kh * kw times the image): the batch runs in "
+     "chunks of as many images as fit, at least one; depends on shapes and this switch only, never on free memory")
 # ---- Scan ---------------------------------------------------------------------------------------
 _def("SCAN_PERSIST", 1, int, "Scan loops as ONE persistent kernel where the class allows")
 _def("ROWS_BYTES_CAP_GB", 0.0, float, "bytes a whole-sequence evaluation of a Scan without recurrence may allocate before "

@@ -28,6 +28,7 @@ from .lower import lower_fgraph
 # the query below names rewrites of tensor/nnet/basic.py: they must be registered before a query
 # mentions them (a RewriteDatabase refuses to register a name that a query has already created)
 import aesara.tensor.nnet.basic  # noqa: E402,F401  isort:skip
+import aesara.tensor.nnet.rewriting  # noqa: E402,F401  isort:skip  (conv_opts, AbstractConvCheck)
 
 HIP_QUERY = RewriteDatabaseQuery(
     include=["fast_run"],
@@ -41,7 +42,18 @@ HIP_QUERY = RewriteDatabaseQuery(
              "local_softmax_grad_to_crossentropy_with_softmax_grad",
              "local_crossentropy_to_crossentropy_with_softmax_grad", "local_argmax_pushdown",
              "local_advanced_indexing_crossentropy_onehot",
-             "local_advanced_indexing_crossentropy_onehot_grad"],
+             "local_advanced_indexing_crossentropy_onehot_grad",
+             # tensor/nnet/rewriting.py: every rewrite that replaces the abstract convolution Ops by a
+             # CPU implementation ("conv_opts"), and the check that raises when one is left
+             # ("AbstractConvCheck", position 48.7).  At the reference's revision that path is broken:
+             # local_abstractconv_gemm builds a CorrMM whose make_node (tensor/nnet/corr.py:695)
+             # calls tuple(a, b, c, d) -> TypeError; local_conv2d_cpu / local_conv2d_gradweight_cpu /
+             # local_conv2d_gradinputs_cpu then fail on ConvOp.__init__() got an unexpected keyword
+             # argument 'version' / 'direction_hint'; AbstractConvCheck finally raises
+             # MetaNodeRewriterSkip("AbstractConv2d Aesara rewriting failed").  The abstract Ops
+             # themselves work (perform: SciPy's convolve2d) and are what lower_conv.py lowers; graphs
+             # without a convolution are untouched by the two names.
+             "conv_opts", "AbstractConvCheck"],
 )
 
 

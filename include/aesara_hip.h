@@ -469,6 +469,24 @@ int ahip_fft_c2c(int dtype, int inverse, const void* x, int64_t outer, int64_t n
 int ahip_fft_c2r(int dtype, const void* x, int64_t outer, int64_t n, int64_t inner, int64_t valid,
                  int64_t x_so, int64_t x_sn, int64_t x_si, void* out, int64_t o_so, int64_t o_sn,
                  int64_t o_si, void* ws, size_t ws_bytes, void* stream);
+/* ---- K15: im2col / col2im of the 2-d convolution ---------------------------------------------
+ * replaces the layout half of tensor/nnet/abstract_conv.py:2501 AbstractConv.perform, :2834
+ * AbstractConv_gradWeights.perform and :3191 AbstractConv_gradInputs.perform; the products run on
+ * ahip_gemm / ahip_gemm_batched.  dtype: AHIP_F32 or AHIP_F64.
+ *   col[n][(c*kh + i)*kw + j][oh*OW + ow] = x[n, c, oh*sh - pad_top + i*dh, ow*sw - pad_left + j*dw],
+ * zero where that position lies in the padding; col is contiguous [N][C*kh*kw][OH*OW].
+ * im2col reads x through its four element strides (n, c, h, w; any sign).  col2im is the adjoint as
+ * a gather: out[n, c, h, w] (contiguous [N][C][H][W]) is the sum, for i then j ascending, of the
+ * entries of col that im2col would have read from that element — no atomics, a fixed order.
+ * Pixel coordinates are 32-bit: H*W, OH*OW, OH*sh, OW*sw and the dilated kernel extent plus padding
+ * each stay below 2^30 (AHIP_EINVAL otherwise); element offsets are 64-bit.                       */
+int ahip_im2col2d(int dtype, const void* x, const int64_t* x_strides, int64_t N, int64_t C,
+                  int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t pad_top, int64_t pad_left,
+                  int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t OH, int64_t OW, void* col,
+                  void* stream);
+int ahip_col2im2d(int dtype, const void* col, int64_t N, int64_t C, int64_t H, int64_t W,
+                  int64_t kh, int64_t kw, int64_t pad_top, int64_t pad_left, int64_t sh, int64_t sw,
+                  int64_t dh, int64_t dw, int64_t OH, int64_t OW, void* out, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
