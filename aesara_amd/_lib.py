@@ -139,6 +139,7 @@ SIGNATURES = {
                                         i32, i32, i32, vp]),
     "ahip_gemm": (i32, [i32, i64, i64, i64, vp, vp, i64, i64, vp, i64, i64, vp, vp, i64, i64,
                         vp, i64, i64, vp]),
+    "ahip_gemm_last_route": (C.c_char_p, []),
     "ahip_gemm_ws_bytes": (sz, [i32, i64, i64, i64, i64]),
     "ahip_gemm_splitk": (i32, [i32, i64, i64, i64, vp, vp, i64, i64, vp, i64, i64, vp, vp, i64, i64,
                                vp, i64, i64, vp, sz, vp]),

@@ -65,6 +65,12 @@ size_t ahip_reduce_ws_bytes(void) { return (size_t)AHIP_MAX_PARTIALS * (16 + 64)
 
 int ahip_set_param(const char* name, int64_t value) {
   if (name != nullptr && !strcmp(name, "reduce_row_blocks_per_cu") && value > 0) { g_reduce_row_blocks_per_cu = value; return AHIP_OK; }
+  // GEMM parameters whose defaults are not positive: they must be settable (a test that forces a
+  // route has to put the default back): 0 tiles = never the 16-row kernels, nf 0 = by grid size,
+  // ksplit -1 = by workgroup count
+  if (name != nullptr && !strcmp(name, "gemm_small_max_tiles") && value == 0) { ahip_gemm_set_small_max_tiles(0); return AHIP_OK; }
+  if (name != nullptr && !strcmp(name, "gemm_skinny_nf") && value == 0) { ahip_gemm_set_skinny_nf(0); return AHIP_OK; }
+  if (name != nullptr && !strcmp(name, "gemm_half_ksplit") && value == -1) { ahip_gemm_set_half_ksplit(-1); return AHIP_OK; }
   AHIP_REQUIRE(name != nullptr && value > 0, "bad parameter");
   if (!strcmp(name, "stream_blocks_per_cu")) g_stream_blocks_per_cu = value;
   else if (!strcmp(name, "reduce_blocks_per_cu")) g_reduce_blocks_per_cu = g_reduce_flat_blocks_per_cu = value;

@@ -83,6 +83,17 @@ AHIP_PTRS_BEGIN(GemmArgs) AHIP_PTR1(A) AHIP_PTR1(B) AHIP_PTR1(Cin) AHIP_PTR1(C) 
 
 void set_limits(GemmArgs& g, int64_t isz);
 
+// the instantiation the last ahip_gemm* call on this thread launched (ahip_gemm_last_route):
+// recorded by the launchers themselves, next to the launch, as a format and its numbers (a few
+// stores per call); the name is only put together when somebody asks for it
+struct RouteRec { const char* fmt; int v[4]; int slices; };
+thread_local RouteRec g_route = {"none", {0, 0, 0, 0}, 0};
+thread_local char g_route_text[64];
+inline void route_set(const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
+  g_route = RouteRec{fmt, {a, b, c, d}, 0};
+}
+#define AHIP_ROUTE(...) route_set(__VA_ARGS__)
+
 // ---- staging ---------------------------------------------------------------------------
 // MODE 0: k is the contiguous axis (unit stride along k, vectorisable)
 // MODE 1: the row axis (m for A, n for B) is contiguous (register transpose)
@@ -809,6 +820,7 @@ template <typename T>
 int launch_tn(const GemmArgs& g, int64_t batch, hipStream_t s) {
   constexpr int TILE = 16 * Traits<T>::VEC;
   const int64_t gx = (g.N + TILE - 1) / TILE, gy = (g.M + TILE - 1) / TILE;
+  AHIP_ROUTE("tn");
   AHIP_LAUNCH((gemm_tn_kernel<T>), dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), dim3(256), 0,
               s, g);
   return AHIP_OK;
@@ -822,10 +834,13 @@ int launch_skinny(const GemmArgs& g, int64_t batch, hipStream_t s) {
   // rate: split K over more wavefronts (batch-64 recurrent step: 12.7 -> 9.7 ms per 512 steps)
   const int64_t wgs = gx * gy * batch;
   if (NF <= 2 && wgs <= 512 && g.K >= 1024) {
+    AHIP_ROUTE("skinny/nf%d/bkc%d/nw16", NF, (int)BKC);
     AHIP_LAUNCH((gemm_skinny_kernel<T, NF, BKC, 16>), grid, dim3(1024), 0, s, g);
   } else if (wgs <= 1024 && g.K >= 512) {
+    AHIP_ROUTE("skinny/nf%d/bkc%d/nw8", NF, (int)BKC);
     AHIP_LAUNCH((gemm_skinny_kernel<T, NF, BKC, 8>), grid, dim3(512), 0, s, g);
   } else {
+    AHIP_ROUTE("skinny/nf%d/bkc%d/nw4", NF, (int)BKC);
     AHIP_LAUNCH((gemm_skinny_kernel<T, NF, BKC, 4>), grid, dim3(256), 0, s, g);
   }
   return AHIP_OK;
@@ -868,6 +883,7 @@ int launch_small(const GemmArgs& g, int64_t batch, hipStream_t s) {
       return launch_skinny<T, 1, false>(g, batch, s);
     }
   }
+  AHIP_ROUTE("small");
   AHIP_LAUNCH((gemm_small_kernel<T>), dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), dim3(256),
               0, s, g);
   return AHIP_OK;
@@ -892,6 +908,8 @@ int operand_mode(const void* p, int64_t rs, int64_t ks, int64_t rows, int64_t K,
 template <typename T, int AM, int BMd, int EDGE, int H = 0, int KS = 1>
 int launch_gemm(const GemmArgs& g, int64_t batch, hipStream_t s) {
   constexpr size_t lds = KS * 2 * (Cfg<H>::BM + Cfg<H>::BN) * ROW_BYTES;
+  if (H) AHIP_ROUTE("half/a%d/b%d/e%d/ks%d", AM, BMd, EDGE, KS);
+  else AHIP_ROUTE("big/a%d/b%d/e%d", AM, BMd, EDGE);
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(
@@ -964,6 +982,7 @@ int gemm_dispatch(GemmArgs& g, int64_t batch, hipStream_t s) {
   if (g.K == 0 || g.alpha == 0.0) {
     int64_t n = g.M * g.N;
     unsigned blocks = (unsigned)(((n + 255) / 256) < 4096 ? ((n + 255) / 256) : 4096);
+    AHIP_ROUTE("scale");
     AHIP_LAUNCH((scale_kernel<T>), dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s, g);
     return AHIP_OK;
   }
@@ -1079,6 +1098,7 @@ int gemm_splitk(const GemmArgs& g, int64_t S, void* ws, hipStream_t s) {
   int bm = operand_mode<T>(p.B, p.b_cs, p.b_rs, p.N, p.K, p.b_bs, S);
   int rc = run_big<T>(p, am, bm, S, s);
   if (rc) return rc;
+  g_route.slices = (int)S;   // "splitk/s{S}/" in front of the big route run_big recorded
   SplitArgs r{ws, g.Cin, g.C, g.M, g.N, S, g.ci_rs, g.ci_cs, g.c_rs, g.c_cs, g.alpha, g.beta};
   int64_t n = g.M * g.N;
   unsigned blocks = (unsigned)(((n + 255) / 256) < 2048 ? ((n + 255) / 256) : 2048);
@@ -1130,6 +1150,7 @@ int ahip_gemm_batched(int dtype, int64_t batch, int64_t M, int64_t N, int64_t K,
   g.Cin = (g.beta != 0.0) ? Cin : C; g.ci_bs = ci_bs; g.ci_rs = ci_rs; g.ci_cs = ci_cs;
   g.C = C; g.c_bs = c_bs; g.c_rs = c_rs; g.c_cs = c_cs;
   g.tiles_m = g.tiles_n = 0;
+  AHIP_ROUTE("none");
   set_limits(g, dtype == AHIP_F32 ? 4 : 8);
   if (M > 0 && N > 0 && batch > 0) {
     AHIP_REQUIRE(C != nullptr, "null C");
@@ -1160,6 +1181,15 @@ int ahip_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* alpha, con
               int64_t c_rs, int64_t c_cs, void* stream) {
   return ahip_gemm_batched(dtype, 1, M, N, K, alpha, A, 0, a_rs, a_cs, B, 0, b_rs, b_cs, beta,
                            Cin, 0, ci_rs, ci_cs, C, 0, c_rs, c_cs, stream);
+}
+
+const char* ahip_gemm_last_route(void) {
+  int k = 0;
+  if (g_route.slices)
+    k = snprintf(g_route_text, sizeof(g_route_text), "splitk/s%d/", g_route.slices);
+  snprintf(g_route_text + k, sizeof(g_route_text) - k, g_route.fmt, g_route.v[0], g_route.v[1],
+           g_route.v[2], g_route.v[3]);
+  return g_route_text;
 }
 
 size_t ahip_gemm_ws_bytes(int dtype, int64_t batch, int64_t M, int64_t N, int64_t K) {

@@ -176,7 +176,9 @@ int ahip_stream_synchronize(void* stream);
  * "gemm_small_max_tiles" (default 64: below that many 128x128 tiles ahip_gemm uses the
  * 16x16-tile split-K kernel that gives every CU work on small outputs), "gemm_skinny_nf",
  * "gemv_col_blocks_per_cu" (default 4) and "gemv_col_strip_lanes" (default 128: lanes x 16 B
- * of every row per workgroup in the transposed-matrix GEMV)                                    */
+ * of every row per workgroup in the transposed-matrix GEMV).  Values are positive, except the
+ * defaults of three GEMM parameters, which can be put back: "gemm_small_max_tiles" 0 (never),
+ * "gemm_skinny_nf" 0 (by grid size), "gemm_half_ksplit" -1 (by workgroup count)                */
 int ahip_set_param(const char* name, int64_t value);
 
 /* ---- runtime compilation of generated kernels ------------------------------------------
@@ -303,6 +305,16 @@ int ahip_igemm_batched(int dtype, int64_t batch, int64_t M, int64_t N, int64_t K
                        int64_t a_bs, int64_t a_rs, int64_t a_cs, const void* B, int64_t b_bs,
                        int64_t b_rs, int64_t b_cs, void* C, int64_t c_bs, int64_t c_rs, int64_t c_cs,
                        void* stream);
+/* Which kernel instantiation the last ahip_gemm / ahip_gemm_batched / ahip_gemm_splitk call on this
+ * thread launched (a thread-local string, written by the launchers; for tests and tuning tools):
+ *   big/a{0,1,2}/b{0,1,2}/e{0,1,2}       128x128 tile: staging mode of A, of B, edge mode
+ *   half/a./b./e{0,2}/ks{1,2,4}          64x64 tile and its K groups
+ *   skinny/nf{1,2,4}/bkc{0,1}/nw{4,8,16} 16-row vector-load kernel
+ *   tn, small, scale                     the standalone kernels
+ *   splitk/s{S}/big/...                  S slices of the big kernel, then the reduction
+ *   none                                 nothing was launched (M, N or batch zero)
+ * A plain addition to the ABI: AHIP_ABI_VERSION changes only when an existing entry point does.  */
+const char* ahip_gemm_last_route(void);
 /* Split-K form for few output tiles and a very long K (weight gradients X.T @ dY): the K range runs
  * as S slices of the 128x128 kernel into the caller-provided workspace [S][M][N], then one pass
  * sums the slices in order and applies alpha / beta (deterministic).  ahip_gemm_ws_bytes returns

@@ -90,7 +90,9 @@ def test_ragged_gemm_sizes_and_offsets():
         z = torch.zeros(M, N, dtype=torch.float64, device="cuda")
         (out,) = ex(z, x, y)
         assert torch.allclose(out, x @ y, rtol=1e-12, atol=1e-12)
-    # misaligned (odd element offset) views force the scalar staging path
+    # misaligned (odd element offset) views: at this size (2 big tiles) that is the scalar-load
+    # 16x16 kernel (gemm_small_kernel), not the big tile's scalar staging — the latter is
+    # forced and checked in tests/test_gpu_gemm_routes.py (big/a2/*, big/*/b2)
     big = torch.randn(130, 131, dtype=torch.float64, device="cuda")
     x, y = big[1:129, 1:130], big[:129, 2:131]
     (out,) = ex(torch.zeros(128, 129, dtype=torch.float64, device="cuda"), x, y)

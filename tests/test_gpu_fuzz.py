@@ -274,7 +274,12 @@ def test_random_indexing_plans_are_bit_exact(seed):
 def test_random_blas_shapes_and_layouts(seed):
     """Gemm / Gemv / Ger / BatchedDot with random extents (0, 1, ragged, around the tile edges),
     operand layouts (row-major, transposed, stepped views) and alpha / beta, against an fp64
-    NumPy restatement: Frobenius-relative 2e-6 in fp32 (the bar of BASELINE config 3b), 1e-13 fp64."""
+    NumPy restatement: Frobenius-relative 2e-6 in fp32 (the bar of BASELINE config 3b), 1e-13 fp64.
+
+    At these extents (<= 257: at most 9 tiles of 128 x 128) the dispatcher sends every product to the
+    16-row kernels (skinny / tn / small); the 128 x 128 and 64 x 64 tiles, their edge and staging modes
+    and split-K are run one instantiation at a time, element by element, in
+    tests/test_gpu_gemm_routes.py."""
     from aesara_amd.executor import PlanExecutor
     from aesara_amd.plan import Node, Plan, Var
     rng = np.random.default_rng(3000 + seed)
