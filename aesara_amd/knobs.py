@@ -76,36 +76,17 @@ _def("SP_SLEEP", 1, int, "s_sleep between polls of the vector-state kernel")
 _def("SP_DELAY", 15, int, "vector-state kernel: s_sleep units (64 cycles) before the first poll of a hand-off "
      "(config 4 B = 1, 128 x 8 rows, 2 polling waves: 4.59 us per step with 0, 4.05 with 12, 4.27 with 20; "
      "256 x 4 rows, 4 polling waves: 3.52 / 3.42 / 3.38 / 3.37 / 3.43 with 10 / 12 / 14 / 16 / 18)")
-_def("SP_EARLYDOTS", 1, int, "vector-state kernel: products on operands staged by an earlier phase of the step are "
-     "issued in front of the phase's hand-off wait (0: behind it, the round-5 order)")
 _def("SP_TRACE", 0, int, "vector-state kernel: stamp s_memtime at the phase marks (tools/sp_trace.py)")
-_def("SM_CHUNK", 32, int, "k-chunk of the matrix-state kernel's exchange")
-_def("SM_XMODE", None, str, "exchange form of the matrix-state kernel: frag | flag (default by registers)")
-_def("SM_EARLY", "first", str, "which product of a step starts before the hand-off: first | none")
-_def("SM_PIN", None, int, "fragment form: pin the recurrent weights to architectural (1) or accumulation (2) "
-     "registers, 0 = leave them to the allocator (default: 2 with in-loop sequence products, else 1)")
 _def("SM_TRACE", 0, int, "stamp s_memtime at the phase marks (tools/sm_trace.py)")
-_def("SM_FENCE", 1, int, "scheduler fences at the phase marks")
-_def("SM_INIT", "publish", str, "fragment form, initial state: branch (step 0 reads the output buffer) | publish "
-     "(every workgroup publishes its tile before the loop: no step-0 code in the loop)")
-_def("SM_XRELOAD", "late", str, "in-loop sequence products: the next x is requested behind the MFMAs of the first "
-     "product on the fetched operand (late) | of the next phase's product on staged operands (early)")
-_def("SM_ACKFILL", 1, int, "the next phase's products on staged operands are issued before the wait for the "
-     "acknowledgement of this phase's payload stores")
-_def("SM_EPRE", 6, int, "with SM_ACKFILL: fragments (of 16) of the staged-operand product issued before the "
-     "acknowledgement wait, the rest behind the tag (0 = all of them before)")
+_def("SM_EPRE", 6, int, "in-loop sequence products: the next phase's product on staged operands is begun before the "
+     "wait for the acknowledgement of this phase's payload stores — this many fragments (of 16) of it, the "
+     "rest behind the tag (0 = all of them before)")
 _def("SM_ELOOK", 6, int, "fragments of the rest of that product issued before the first look at the next tags "
      "(0 = the look belongs to the window, SM_LOOK)")
 _def("SM_XSPLIT", 4, int, "fragments of a wrapped sequence product that stay in the last window of the step; the "
      "others move to the first window of the next step (0 = all stay)")
 _def("SM_XPRE", 6, int, "fragments of the next step's first sequence-product window issued before the wait for "
      "the acknowledgement of the last phase's payload stores")
-_def("SM_NXT", "fetch", str, "per-step sequence operands of the epilogue: requested at the top of the step (top) | "
-     "behind the first fetch of the step (fetch: an HBM-cold load in front of the fetch delays every "
-     "in-order wait behind it)")
-_def("SM_POLLS", 1, int, "fragment form: tag polls a wavefront keeps in flight while it waits for a hand-off "
-     "(1 = one at a time.  More find the tags sooner after they arrive but 64 workgroups poll each tag line: "
-     "measured r04, GRU training step 17.7 ms with 1, 18.6 with 4; forward kernel unchanged)")
 _def("SM_SPIN_DELAY", 15, int, "fragment form, fetches with nothing in front of them: s_sleep units (64 cycles) "
      "before the first poll of the tags (a poll that comes back empty costs a whole further round trip AND "
      "slows the tag stores it polls for: GRU training step B = 64 17.7 -> 15.6 ms with 15)")
@@ -117,14 +98,8 @@ _def("SM_BATCH_CHUNKS", 1, int, "a batch whose 16 x 16 tiles outnumber the CUs r
      "2 / 4 / 8 blocks per workgroup: 1 = forward Scans (their in-loop sequence products need one block per "
      "workgroup), 2 = every Scan, 0 = never")
 _def("SM_XFOLD", 1, int, "sequence products x_t @ W inside the loop")
-_def("SM_XREG", 0, int, "1 = in-loop sequence products beyond the LDS capacity keep their weight columns in "
-     "accumulation registers (as many as fit next to the recurrent weights); 0 = those are computed up front "
-     "(config 4, B = 64: the third product in the loop costs 0.6 ms of exposed MFMA time, the GEMM it replaces 0.69 — "
-     "4.30 vs 4.12 ms)")
-_def("SM_INTERLEAVE", 1, int, "interleave the phases of the batch blocks of one workgroup")
 _def("SPIN_LOG2", 21, int, "log2 of the poll limit of the persistent Scan kernels before they raise their error word "
      "(tools/profile_scan_r04.sh raises it: under the counter passes a kernel runs many times slower)")
-_def("SM_DEPTH", 8, int, "16-byte payload loads in flight per lane of the fragment fetch")
 
 
 def names():

@@ -467,7 +467,7 @@ class Spec:
 
     def key(self):
         pr = self.prog
-        blob = json.dumps(["sp9" + ("t" if self.trace else "") + ("" if int(knobs.get("SP_EARLYDOTS")) else "n"), sorted(self.prog.older.items()), self.dtype, sorted(self.var.items()), sorted(self.place.items()), self.M, sorted(self.Ks.items()), sorted(self.lens.items()),
+        blob = json.dumps(["sp9" + ("t" if self.trace else ""), sorted(self.prog.older.items()), self.dtype, sorted(self.var.items()), sorted(self.place.items()), self.M, sorted(self.Ks.items()), sorted(self.lens.items()),
                            self.R, self.nw, sorted(pr.seq.items()), sorted(pr.state.items()),
                            sorted(pr.nsq.items()), sorted(pr.mats.items()),
                            [[ph["dots"], ph["ins"], ph["outs"], ph["scalar"], ph["out_refs"]]
@@ -735,18 +735,17 @@ def generate(spec: Spec):
         #    FMAs run while the granules this phase waits for are still on their way (GRU: the z-gate
         #    product U_z h sits in the phase that waits for r * h)
         early_dots = set()
-        if int(knobs.get("SP_EARLYDOTS")):
-            for d, (a_, x) in enumerate(ph["dots"]):
-                if x in pr.nsq or (x, "prev" if x in pr.state else ("cur" if x not in pr.seq else "glob")) \
-                        in staged_this_step:
-                    early_dots.add(d)
-            if len(early_dots) == len(ph["dots"]):
-                early_dots = set()            # nothing to wait for in this phase: the plain order
-            for d, (a_, x) in enumerate(ph["dots"]):
-                if d in early_dots:
-                    emit_dot(pi, d, a_, x)
-            if early_dots:
-                stamp("p%d early dots" % pi)
+        for d, (a_, x) in enumerate(ph["dots"]):
+            if x in pr.nsq or (x, "prev" if x in pr.state else ("cur" if x not in pr.seq else "glob")) \
+                    in staged_this_step:
+                early_dots.add(d)
+        if len(early_dots) == len(ph["dots"]):
+            early_dots = set()            # nothing to wait for in this phase: the plain order
+        for d, (a_, x) in enumerate(ph["dots"]):
+            if d in early_dots:
+                emit_dot(pi, d, a_, x)
+        if early_dots:
+            stamp("p%d early dots" % pi)
         # -- gather the dot vectors that are not staged yet
         need_sync = False
         delayed = False     # the first exchanged operand of a phase waits before its first poll

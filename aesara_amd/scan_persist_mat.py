@@ -10,8 +10,10 @@ instead of 2 launches per step that re-stream 12 MiB of weights from the memory-
   weight columns of every matrix in VGPRs in MFMA B-operand layout for the whole loop
   (K / 16 registers per matrix: 192 for config 4) — weights are read from HBM once per eval;
 * the A operand (the 16 x K block of ``h`` or ``r*h`` that belongs to batch block ``bi``) is what
-  the 64 workgroups of that block exchange: every workgroup publishes its 256 tile values as
-  tagged 8-byte granules and polls the 16 x K block (chunks of 16 granules per thread) into a
+  the 64 workgroups of that block exchange: every workgroup publishes its 256 tile values,
+  waits for the stores' acknowledgement and raises ONE tag word; consumers poll the tags of their
+  producers and pull the block — in the FRAGMENT form (``_generate_frag``, below) straight into
+  the registers the MFMAs read, else (weights + live fragments beyond 320 registers) into a
   padded LDS image (pitch K + 4: conflict-free ``ds_read_b128`` in MFMA A layout);
 * ``v_mfma_f32_16x16x4_f32`` over the wave's K quarter, partial tiles summed in wave order through
   LDS, one thread per tile element runs the epilogue, keeps its state / sequence operands in
@@ -31,11 +33,16 @@ operand blocks that lend each other their LDS slot, and state widths that are no
 64 (``SpecMat.Nt``: the executor zero-pads the weights, unowned columns are never published).
 
 Round 3 added the FRAGMENT form of the exchange (``_generate_frag``: payload in MFMA A-fragment
-order, pulled straight into the registers the MFMAs read — the default whenever the weight columns
+order, pulled straight into the registers the MFMAs read — chosen whenever the weight columns
 and the operand fragments alive at the same time fit in 320 registers, which now includes the
 gradient kernels) and, on it, the sequence products ``x_t @ W`` computed INSIDE the loop
 (``xfold_pairs`` / ``xfold_windows`` / ``emit_window``: weight columns in LDS, ``x`` in fragment
 order a step ahead, the work placed in the idle windows in front of each operand fetch).
+Round 4 scheduled the hand-offs of that form: the initial state published through the exchange
+(no step-0 path in the loop), MFMAs that need nothing from a hand-off issued in front of its
+acknowledgement wait, the first look at the next tags placed where it finds them.  There is ONE
+schedule; its numbers (``SpecMat.epre`` … ``xsplit``) are switches, the alternatives that were
+measured and lost are in docs/HISTORY.md.
 DESIGN.md §3.3b has the timelines each of these decisions came from.
 """
 from __future__ import annotations
@@ -109,11 +116,9 @@ class SpecMat:
         self.Nt = N if Nt is None else Nt
         self.NB = -(-B // 16)
         self.NJ = N // 16
-        # granule loads a thread keeps in flight per polling pass (2 VGPRs each)
-        self.chunk = int(knobs.get("SM_CHUNK"))
         # exchange form: "flag" = untagged 8-byte float pairs + ONE tag word per producing
-        # workgroup (half the bytes, one polling pass); "granule" = {tag, value} per element
-        #   "frag" (default when the registers allow it) = the flag form with the payload laid out
+        # workgroup, polled into an LDS image of the operand block
+        #   "frag" (whenever the registers allow it) = the flag form with the payload laid out
         #   in MFMA A-FRAGMENT order: a consumer wavefront polls only the tags of the producers of
         #   ITS K quarter and pulls that quarter with coalesced 16-byte sc1 loads straight into the
         #   registers the MFMAs read — no LDS image, no staging pass, no barrier between hand-off
@@ -140,54 +145,50 @@ class SpecMat:
         if xfold:
             self.xmode = "frag"
         else:
-            self.xmode = knobs.get("SM_XMODE") or ("frag" if regs <= 320 else "flag")
+            self.xmode = "frag" if regs <= 320 else "flag"
         if dtype == "float64" and not xfold:
             self.xmode = "frag" if regs <= 384 else "none"     # float64 exists in the fragment form only
-        # products on operands that are already in registers run BEFORE the wait for the new
-        # operand's tags (r03 timeline, config 4 B = 64: 6.7 us per step; issuing them after the
-        # loads — to cover the load latency instead of the tag latency — measured 8.5)
-        self.early_first = knobs.get("SM_EARLY") == "first"
-        # fragment form: the weight columns pinned to ARCHITECTURAL registers (the fragments the
-        # loads deliver then live in accumulation registers).  Left to the allocator, products
-        # end up with A and B both in AGPRs and get a v_accvgpr_read through ONE temporary in
-        # front of every MFMA (r03 timeline: 64 such MFMAs 1.2 us, 64 plain ones 0.93)
-        #   2 = pinned to ACCUMULATION registers instead (MFMA reads B from either file): the
-        #   fragments and x then stay in the architectural file the loads deliver into
-        pin_k = knobs.get("SM_PIN")
-        pin_k = (2 if xfold else 1) if pin_k is None else int(pin_k)
-        self.pin = pin_k if (self.xmode == "frag" and wpr * sum(K // 16 for K in Ks.values()) <= 192) else 0
+        frag = self.xmode == "frag"
+        # fragment form: the weight columns pinned to ARCHITECTURAL registers (1: the fragments the
+        # loads deliver then live in accumulation registers).  Left to the allocator (0: beyond 192
+        # registers of weights), products end up with A and B both in AGPRs and get a
+        # v_accvgpr_read through ONE temporary in front of every MFMA (r03 timeline: 64 such MFMAs
+        # 1.2 us, 64 plain ones 0.93)
+        #   2 (with in-loop sequence products) = pinned to ACCUMULATION registers instead (MFMA
+        #   reads B from either file): the fragments and x then stay in the architectural file the
+        #   loads deliver into
+        self.pin = (2 if xfold else 1) if (frag and wpr * sum(K // 16 for K in Ks.values()) <= 192) else 0
         # per-phase timeline (tools/sm_trace.py): thread 0 of workgroups 0 and NB*NJ/2 stamps
         # s_memtime at every mark of steps TRACE_T0 .. TRACE_T0+TRACE_NT-1 into ctl[16..]
         self.trace = bool(int(knobs.get("SM_TRACE")))
-        # fragment form schedule:
-        #   init     "publish": every workgroup publishes its tile of the initial state through the
-        #            exchange before the loop — the loop body has no step-0 path (the merge of the two
-        #            paths cost 84 register copies per step and conservative s_waitcnt vmcnt(0))
-        #   xreload  where the next x is requested (16 loads per lane): behind the MFMAs of a product
-        #            that waits for payload ("late": each load finds the queue full of the 16 payload
-        #            loads and stalls the instruction stream) or of one that waits for nothing ("early")
-        #   ackfill / xpre   MFMAs that need nothing from the hand-off, issued between the payload
+        # fragment form: every workgroup publishes its tile of the initial
+        # state through the exchange before the loop — the loop body has no step-0 path (the merge
+        # of the two paths cost 84 register copies per step and conservative s_waitcnt vmcnt(0)).
+        # With sequence products in the loop (one batch block per workgroup, always) the hand-offs
+        # are scheduled around them; the numbers of that schedule, 0 = off:
+        #   epre / xpre   MFMAs that need nothing from the hand-off, issued between the payload
         #            stores and the wait for their acknowledgement (0.35 us per hand-off otherwise idle)
-        self.init = str(knobs.get("SM_INIT")) if self.xmode == "frag" else "branch"
-        sched = self.xmode == "frag" and bool(xfold) and nblk == 1 and self.init == "publish"
-        self.xreload = str(knobs.get("SM_XRELOAD")) if sched else "late"
-        self.ackfill = int(knobs.get("SM_ACKFILL")) if sched else 0
+        #   elook / look  fragments issued before the first look at the next operand's tags
+        #   xsplit   fragments of a wrapped sequence product that stay in the step's last window
+        sched = bool(xfold)
         self.xpre = int(knobs.get("SM_XPRE")) if sched else 0
         self.look = int(knobs.get("SM_LOOK")) if sched else 0
-        self.epre = int(knobs.get("SM_EPRE")) if (sched and self.ackfill) else 0
-        self.elook = int(knobs.get("SM_ELOOK")) if (sched and self.ackfill) else 0
+        self.epre = int(knobs.get("SM_EPRE")) if sched else 0
+        self.elook = int(knobs.get("SM_ELOOK")) if sched else 0
         self.xsplit = int(knobs.get("SM_XSPLIT")) if sched else 0
-        self.nxt = str(knobs.get("SM_NXT")) if self.xmode == "frag" else "top"
-        self.polls = int(knobs.get("SM_POLLS")) if self.xmode == "frag" else 1
-        self.spin_delay = int(knobs.get("SM_SPIN_DELAY")) if self.xmode == "frag" else 0
+        self.spin_delay = int(knobs.get("SM_SPIN_DELAY")) if frag else 0
 
     def key(self):
         pr = self.prog
-        blob = json.dumps(["sm9" + ("t" if self.trace else "") + ("/f5p%d%s" % (self.pin, str(knobs.get("SM_FENCE"))) if self.xmode == "frag" else ""), self.xfold and [self.xfold, "w15", str(knobs.get("SM_XTAIL"))], [self.init, self.xreload, self.ackfill, self.xpre, self.look, self.nxt, self.epre, self.elook, self.xsplit, self.polls, self.spin_delay], self.dtype, self.chunk, self.xmode, self.early_first, self.B, self.N, self.Nt, sorted(self.Ks.items()), sorted(pr.seq.items()),
+        frag, sched = self.xmode == "frag", bool(self.xfold)
+        # (the string and number literals — "publish", "late", "fetch", 1, 32, True, "1" … — stand
+        # where choices that are no longer made were hashed: frozen parts of the cache key, and
+        # through the kernel's name of its source)
+        blob = json.dumps(["sm9" + ("t" if self.trace else "") + ("/f5p%d1" % self.pin if frag else ""), self.xfold and [self.xfold, "w15", str(knobs.get("SM_XTAIL"))], ["publish" if frag else "branch", "late", 1 if sched else 0, self.xpre, self.look, "fetch" if frag else "top", self.epre, self.elook, self.xsplit, 1, self.spin_delay], self.dtype, 32, self.xmode, True, self.B, self.N, self.Nt, sorted(self.Ks.items()), sorted(pr.seq.items()),
                            sorted(pr.state.items()), sorted(pr.older.items()), sorted(pr.depth.items()), sorted(pr.nsq.items()), sorted(pr.mats.items()),
                            [[ph["dots"], ph["ins"], ph["outs"], ph["scalar"], ph["out_refs"]]
                             for ph in pr.phases], pr.outs, pr.exchanged, sorted(pr.tap_seq.items())] +
-                          ([["nblk", self.nblk, str(knobs.get("SM_INTERLEAVE"))]] if self.nblk != 1 else []),
+                          ([["nblk", self.nblk, "1"]] if self.nblk != 1 else []),
                           sort_keys=True)
         return hashlib.sha256(blob.encode()).hexdigest()[:24]
 
@@ -308,18 +309,11 @@ def xfold_windows(prog, pairs):
     return {"win": win, "wrapped": wrapped, "reload": fetch[-1], "ahead": 2}
 
 
-def xch_layout(prog, NB, N, xmode="flag", itemsize=4):
-    """u64 offsets of the exchange buffer.  granule form: per exchanged matrix 4 slots of NB
-    blocks of 16 x N granules -> {var: (offset, slot length)}.  flag form: 4 slots of
-    NB x 16 x N/2 float pairs followed by 4 slots of NB x NJ tag words ->
+def xch_layout(prog, NB, N, itemsize=4):
+    """u64 offsets of the exchange buffer: per exchanged matrix 4 slots of NB x 16 x N/2 float
+    pairs followed by 4 slots of NB x NJ tag words ->
     {var: (payload offset, payload slot length, flag offset, flag slot length)}."""
     off, total = {}, 0
-    if xmode == "granule":
-        lp = NB * 16 * N
-        for v in prog.exchanged:
-            off[v] = (total, lp)
-            total += 4 * lp
-        return off, total
     # ("flag" and "frag" share this layout; "frag" orders the payload of a block by MFMA fragment)
     lpp, lpf = NB * 16 * N * itemsize // 8, NB * (N // 16)
     for v in prog.exchanged:
@@ -363,10 +357,8 @@ def generate(spec: SpecMat):
     name = "sm_" + spec.key()
     AG = "__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT"
     L = [cg.PRELUDE, SM_STRUCT, "typedef unsigned u4v __attribute__((ext_vector_type(4)));"]
-    xoff, _tot = xch_layout(pr, NB, N, spec.xmode, 8 if spec.dtype == "float64" else 4)
-    FRAG = spec.xmode == "frag"
-    FLAG = spec.xmode in ("flag", "frag")
-    if FRAG:
+    xoff, _tot = xch_layout(pr, NB, N, 8 if spec.dtype == "float64" else 4)
+    if spec.xmode == "frag":
         return _generate_frag(spec, name, xoff, _tot)
 
     # staged operand blocks (LDS images, pitch K + 4 floats)
@@ -384,9 +376,8 @@ def generate(spec: SpecMat):
     L.append("  const int vrows = (%d - bi * 16) < 16 ? (%d - bi * 16) : 16;   // valid rows of this batch block" % (B, B))
     L.append("  const unsigned base = __hip_atomic_load(a.ctl, %s);" % AG)
     L.append("  unsigned* errp = a.ctl + 1;")
-    if FLAG:
-        L.append("  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, %du, 0x00020000);"
-                 % (_tot * 8))
+    L.append("  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, %du, 0x00020000);"
+             % (_tot * 8))
     if spec.trace:
         L.append("  const bool tr_on = tid == 0 && (blockIdx.x == 0 || blockIdx.x == %d);" % (NB * NJ // 2))
         L.append("  unsigned long long* tr = (unsigned long long*)(a.ctl + 16) + (blockIdx.x == 0 ? 0 : %d);"
@@ -488,7 +479,7 @@ def generate(spec: SpecMat):
             kind = "prev" if x in pr.state else "cur"
             if (x, kind) not in staged_this_step and (x, kind) not in fresh:
                 fresh.append((x, kind))
-        if FLAG and len(fresh) >= 2 and all(k_ == "cur" for _x, k_ in fresh):
+        if len(fresh) >= 2 and all(k_ == "cur" for _x, k_ in fresh):
             # several operands published by the same epilogue (the two last-phase products of a
             # gradient step): ONE polling pass over all their tags, all bulk loads in flight
             # together, then per operand  LDS image -> barrier -> its products, so the MFMAs of
@@ -556,9 +547,6 @@ def generate(spec: SpecMat):
             staged_this_step.add((x, kind))
             newly.append((x, kind))
             P = K + 4
-            per_thread = 16 * K // 256          # granules per thread (K % 64 == 0)
-            nchunk = max(1, per_thread // spec.chunk)
-            cl = per_thread // nchunk           # loads per thread per chunk
             src = pr.new_of_state.get(x, x)
             if kind == "prev":
                 k_out = pr.state[x]
@@ -576,59 +564,33 @@ def generate(spec: SpecMat):
                 L.append("    {")
                 step_expr = "t"
             ind = "      "
-            if FLAG:
-                po_, lpp, fo_, lpf = xoff[src]
-                PT = 16 * K // 2 // 256          # float pairs per thread
-                L.append(ind + "const unsigned long long want64 = (unsigned long long)(base + (unsigned)%s + 1u);" % step_expr)
-                L.append(ind + "if (wave == 0) {")
-                L.append(ind + "  const u64* fl = a.xch + %d + (%s & 3) * %d + (i64)bi * %d;" % (fo_, step_expr, lpf, NJ))
-                L.append(ind + "  for (int spin = 0;; ++spin) {")
-                L.append(ind + "    bool ok = true;")
-                L.append(ind + "    for (int j = lane; j < %d; j += 64) ok = ok && (__hip_atomic_load(fl + j, %s) == want64);" % (NJ, AG))
-                L.append(ind + "    if (__all(ok)) break;")
-                L.append(ind + "    if (spin > %d || ((spin & 255) == 255 && __hip_atomic_load(errp, %s) != 0u)) "
-                         "{ __hip_atomic_store(errp, 1u, %s); break; }" % (SPIN_LIMIT, AG, AG))
-                L.append(ind + "    __builtin_amdgcn_s_sleep(1);")
-                L.append(ind + "  }")
-                L.append(ind + "}")
-                L.append(ind + "__syncthreads();")
-                stamp("p%d flags seen" % pi)
-                PT = 16 * K // 4 // 256          # float4 per thread
-                L.append(ind + "const unsigned so_ = (unsigned)((%d + (%s & 3) * %d + (i64)bi * %d) * 8);"
-                         % (po_, step_expr, lpp, 16 * K // 2))
-                L.append(ind + "u4v g[%d];" % PT)
-                for u in range(PT):
-                    L.append(ind + "{ const int idx = %d * 256 + tid; const u4v z_ = {0u, 0u, 0u, 0u}; g[%d] = (idx / %d < vrows) ? "
-                             "__builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)idx * 16u, so_, 16) : z_; }"
-                             % (u, u, K // 4))
-                for u in range(PT):
-                    L.append(ind + "{ const int idx = %d * 256 + tid; "
-                             "*(u4v*)(Hl + %d + (idx / %d) * %d + 4 * (idx %% %d)) = g[%d]; }"
-                             % (u, so, K // 4, P, K // 4, u))
-                L.append("    }")
-                continue
-            xo, lp = xoff[src]
-            L.append(ind + "const u64* src = a.xch + %d + (%s & 3) * %d + (i64)bi * %d;" % (xo, step_expr, lp, 16 * K))
-            L.append(ind + "const unsigned want = base + (unsigned)%s + 1u;" % step_expr)
-            L.append(ind + "for (int ch = 0; ch < %d; ++ch) {" % nchunk)
-            L.append(ind + "  u64 g[%d];" % cl)
+            po_, lpp, fo_, lpf = xoff[src]
+            L.append(ind + "const unsigned long long want64 = (unsigned long long)(base + (unsigned)%s + 1u);" % step_expr)
+            L.append(ind + "if (wave == 0) {")
+            L.append(ind + "  const u64* fl = a.xch + %d + (%s & 3) * %d + (i64)bi * %d;" % (fo_, step_expr, lpf, NJ))
             L.append(ind + "  for (int spin = 0;; ++spin) {")
             L.append(ind + "    bool ok = true;")
-            for u in range(cl):
-                L.append(ind + "    { const int idx = (ch * %d + %d) * 256 + tid; "
-                         "if (idx / %d < vrows) { g[%d] = __hip_atomic_load(src + idx, %s); "
-                         "ok = ok && ((unsigned)(g[%d] >> 32) == want); } else g[%d] = 0; }"
-                         % (cl, u, K, u, AG, u, u))
-            L.append(ind + "    if (ok) break;")
+            L.append(ind + "    for (int j = lane; j < %d; j += 64) ok = ok && (__hip_atomic_load(fl + j, %s) == want64);" % (NJ, AG))
+            L.append(ind + "    if (__all(ok)) break;")
             L.append(ind + "    if (spin > %d || ((spin & 255) == 255 && __hip_atomic_load(errp, %s) != 0u)) "
                      "{ __hip_atomic_store(errp, 1u, %s); break; }" % (SPIN_LIMIT, AG, AG))
             L.append(ind + "    __builtin_amdgcn_s_sleep(1);")
             L.append(ind + "  }")
-            for u in range(cl):
-                L.append(ind + "  { const int idx = (ch * %d + %d) * 256 + tid; "
-                         "Hl[%d + (idx / %d) * %d + idx %% %d] = __uint_as_float((unsigned)g[%d]); }"
-                         % (cl, u, so, K, P, K, u))
             L.append(ind + "}")
+            L.append(ind + "__syncthreads();")
+            stamp("p%d flags seen" % pi)
+            PT = 16 * K // 4 // 256          # float4 per thread
+            L.append(ind + "const unsigned so_ = (unsigned)((%d + (%s & 3) * %d + (i64)bi * %d) * 8);"
+                     % (po_, step_expr, lpp, 16 * K // 2))
+            L.append(ind + "u4v g[%d];" % PT)
+            for u in range(PT):
+                L.append(ind + "{ const int idx = %d * 256 + tid; const u4v z_ = {0u, 0u, 0u, 0u}; g[%d] = (idx / %d < vrows) ? "
+                         "__builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)idx * 16u, so_, 16) : z_; }"
+                         % (u, u, K // 4))
+            for u in range(PT):
+                L.append(ind + "{ const int idx = %d * 256 + tid; "
+                         "*(u4v*)(Hl + %d + (idx / %d) * %d + 4 * (idx %% %d)) = g[%d]; }"
+                         % (u, so, K // 4, P, K // 4, u))
             L.append("    }")
         D = len(ph["dots"])
         if D:
@@ -649,43 +611,37 @@ def generate(spec: SpecMat):
         L.extend(lines)
         for o, ri in zip(ph["outs"], ph["out_refs"]):
             L.append("      own_%d = %s;" % (o, cg.cast(outs[ri], odts[ri], "float32")))
-            if o in xoff and not FLAG:
-                xo, lp = xoff[o]
-                L.append("      __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + erow * %d + en, "
-                         "((u64)(base + (unsigned)t + 1u) << 32) | (u64)__float_as_uint(own_%d), %s);"
-                         % (xo, lp, 16 * N, N, o, AG))
             for _kind, j in out_of.get(o, []):
                 L.append("      ((float*)a.out[%d])[((a.out_pos0[%d] + t) %% a.out_store[%d]) * a.out_ts[%d] + "
                          "eb * a.out_rs[%d] + en] = own_%d;" % (j, j, j, j, j, o))
         L.append("    }")
-        if FLAG:
-            # Elemwise-only phases run back to back in the element owner's registers: what they
-            # have to publish goes out with ONE store-acknowledge wait and barrier, right before
-            # the next phase that stages an operand (or at the end of the step)
-            pending_pub.extend(o for o in ph["outs"] if o in xoff)
-            nxt_has_dots = pi + 1 < len(pr.phases) and bool(pr.phases[pi + 1]["dots"])
-            pub = pending_pub if (nxt_has_dots or pi + 1 == len(pr.phases)) else []
-            if pub:
-                pending_pub = []
+        # Elemwise-only phases run back to back in the element owner's registers: what they
+        # have to publish goes out with ONE store-acknowledge wait and barrier, right before
+        # the next phase that stages an operand (or at the end of the step)
+        pending_pub.extend(o for o in ph["outs"] if o in xoff)
+        nxt_has_dots = pi + 1 < len(pr.phases) and bool(pr.phases[pi + 1]["dots"])
+        pub = pending_pub if (nxt_has_dots or pi + 1 == len(pr.phases)) else []
+        if pub:
+            pending_pub = []
+        for o in pub:
+            po_, lpp, fo_, lpf = xoff[o]
+            L.append("    { const float nb_ = __shfl_down(own_%d, 1, 64);" % o)
+            L.append("      if (owner && (ecol & 1) == 0) {")
+            L.append("        union { float f[2]; u64 u; } pk; pk.f[0] = own_%d; pk.f[1] = nb_;" % o)
+            L.append("        __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + erow * %d + (en >> 1), pk.u, %s);"
+                     % (po_, lpp, 16 * N // 2, N // 2, AG))
+            L.append("      } }")
+        if pub:
+            stamp("p%d epilogue + payload stores issued" % pi)
+            # payload complete (write-through stores acknowledged) before the tag is raised
+            L.append('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");')
+            stamp("p%d own stores acknowledged" % pi)
+            L.append("    __syncthreads();")
+            stamp("p%d all stores acknowledged" % pi)
             for o in pub:
                 po_, lpp, fo_, lpf = xoff[o]
-                L.append("    { const float nb_ = __shfl_down(own_%d, 1, 64);" % o)
-                L.append("      if (owner && (ecol & 1) == 0) {")
-                L.append("        union { float f[2]; u64 u; } pk; pk.f[0] = own_%d; pk.f[1] = nb_;" % o)
-                L.append("        __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + erow * %d + (en >> 1), pk.u, %s);"
-                         % (po_, lpp, 16 * N // 2, N // 2, AG))
-                L.append("      } }")
-            if pub:
-                stamp("p%d epilogue + payload stores issued" % pi)
-                # payload complete (write-through stores acknowledged) before the tag is raised
-                L.append('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");')
-                stamp("p%d own stores acknowledged" % pi)
-                L.append("    __syncthreads();")
-                stamp("p%d all stores acknowledged" % pi)
-                for o in pub:
-                    po_, lpp, fo_, lpf = xoff[o]
-                    L.append("    if (tid == 0) __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + nj, "
-                             "(unsigned long long)(base + (unsigned)t + 1u), %s);" % (fo_, lpf, NJ, AG))
+                L.append("    if (tid == 0) __hip_atomic_store(a.xch + %d + (t & 3) * %d + (i64)bi * %d + nj, "
+                         "(unsigned long long)(base + (unsigned)t + 1u), %s);" % (fo_, lpf, NJ, AG))
     stamp("step end (tag raised)")
     for v, nv in pr.new_of_state.items():
         L.append("    own_%d = own_%d;" % (v, nv))
@@ -737,10 +693,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     folded = {v for v, _pi, _d, _s in XF}
     L.append('extern "C" __global__ __launch_bounds__(256) void %s(SmArgs a) {' % name)
     L.append("  __shared__ %s part[2][%d][4][256];" % (T, max(ndots_max, 1)))
-    XREG = set(spec.xfold.get("reg", ())) if spec.xfold else set()     # weight columns in registers
-    lds_of = {gi: n for n, gi in enumerate(gi for gi in range(len(XF)) if gi not in XREG)}
-    if lds_of:
-        L.append("  __shared__ __attribute__((aligned(16))) float Wl[%d];" % (len(lds_of) * K * 16))
+    if XF:
+        L.append("  __shared__ __attribute__((aligned(16))) float Wl[%d];" % (len(XF) * K * 16))
     L.append("  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;")
     L.append("  const int r16 = lane & 15, grp = lane >> 4;")
     NBLK = spec.nblk
@@ -780,17 +734,15 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
              % (Q, K // 16, PV, K // 16))
     L.append("  const unsigned ld_off = (unsigned)(((wave * %d) * 64 + lane) * 16);" % Q)
     marks = []
-    FENCE = int(knobs.get("SM_FENCE")) != 0
-
     ASM_MARKS = int(knobs.get("SM_ASM_MARKS")) != 0
 
     def stamp(label):
+        """a phase mark: a scheduler fence, or (trace builds) s_memtime recorded under `label`"""
         if not spec.trace:
-            if FENCE:
+            L.append("    __builtin_amdgcn_sched_barrier(0);")
+            if ASM_MARKS:
+                L.append('    asm volatile("; @@ %s");' % label)
                 L.append("    __builtin_amdgcn_sched_barrier(0);")
-                if ASM_MARKS:
-                    L.append('    asm volatile("; @@ %s");' % label)
-                    L.append("    __builtin_amdgcn_sched_barrier(0);")
             return
         k = len(marks)
         marks.append(label)
@@ -814,18 +766,12 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     # ---- in-kernel sequence products (xfold): the weight columns of x_t @ W_g in LDS, in MFMA
     #      B-fragment order: float4 (w*Q + q)*64 + lane = W_g[w*K/4 + grp*K/16 + 4q .. +3][nj*16 + r16]
     for gi, (_v, _pi, _d, slot) in enumerate(XF):
-        if gi in XREG:          # MFMA B layout in registers, like the recurrent weights
-            L.append("  const i64 wxk%d = (i64)wave * %d + grp * %d;" % (gi, K // 4, K // 16))
-            for s_ in range(K // 16):
-                L.append("  float wx%d_%d = ((const float*)a.mat[%d])[(wxk%d + %d) * a.mat_rs[%d] + nj * 16 + r16];"
-                         % (gi, s_, slot, gi, s_, slot))
-            continue
         L.append("  for (int f = tid; f < %d; f += 256) {" % (K * 16 // 4))
         L.append("    const int ln = f & 63, qq = (f >> 6) %% %d, ww = (f >> 6) / %d;" % (Q, Q))
         L.append("    const i64 k0 = (i64)ww * %d + (ln >> 4) * %d + 4 * qq;" % (K // 4, K // 16))
         L.append("    const float* wp = (const float*)a.mat[%d] + k0 * a.mat_rs[%d] + nj * 16 + (ln & 15);" % (slot, slot))
         L.append("    const f4 wv = {wp[0], wp[a.mat_rs[%d]], wp[2 * a.mat_rs[%d]], wp[3 * a.mat_rs[%d]]};" % (slot, slot, slot))
-        L.append("    *(f4*)(Wl + %d + 4 * f) = wv;" % (lds_of[gi] * K * 16))
+        L.append("    *(f4*)(Wl + %d + 4 * f) = wv;" % (gi * K * 16))
         L.append("  }")
     XW = None
     XTAIL = max(1, int(knobs.get("SM_XTAIL")))  # fragments (4 MFMAs each) behind the payload loads
@@ -843,49 +789,49 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
 
     def emit_xunits(units, ind, between=None):
         """The MFMA k-steps 4q .. 4q+3 of x @ W_<gi> on this wavefront's K quarter into accx<gi>,
-        for every (gi, q) of ``units``.  Weight columns in LDS are read one unit AHEAD into the
+        for every (gi, q) of ``units``.  The weight columns (in LDS) are read one unit AHEAD into the
         other of two registers quads (an LDS read in front of each group of four MFMAs, waited for
         at once, costs as much as the MFMAs).  ``between(i)``: code emitted in front of unit i."""
-        ldsu = [i for i, (gi, _q) in enumerate(units) if gi not in XREG]    # units that read LDS
-        nxt_lds = {ldsu[n]: ldsu[n + 1] for n in range(len(ldsu) - 1)}
-        slot_of = {i: n & 1 for n, i in enumerate(ldsu)}
-        if ldsu:
-            L.append(ind + "bw0 = wl%d[%d];" % (units[ldsu[0]][0], units[ldsu[0]][1] * 64))
+        if units:
+            L.append(ind + "bw0 = wl%d[%d];" % (units[0][0], units[0][1] * 64))
         for i, (gi, q) in enumerate(units):
             if between is not None:
                 between(i)
             if q == 0:
                 L.append(ind + "accx%d_0 = zero4; accx%d_1 = zero4;" % (gi, gi))
-            if gi in XREG:
-                for e, c in enumerate("xyzw"):
-                    L.append(ind + "accx%d_%d = __builtin_amdgcn_mfma_f32_16x16x4f32(xfr[%d].%s, wx%d_%d, accx%d_%d, 0, 0, 0);"
-                             % (gi, e & 1, q, c, gi, 4 * q + e, gi, e & 1))
-                continue
-            if i in nxt_lds:
-                gj, qj = units[nxt_lds[i]]
-                L.append(ind + "bw%d = wl%d[%d];" % (slot_of[nxt_lds[i]], gj, qj * 64))
+            if i + 1 < len(units):
+                gj, qj = units[i + 1]
+                L.append(ind + "bw%d = wl%d[%d];" % ((i + 1) & 1, gj, qj * 64))
                 L.append(ind + "__builtin_amdgcn_sched_barrier(0);     // (the scheduler sinks the read to its use)")
-            bs = ["bw%d.%s" % (slot_of[i], c) for c in "xyzw"]
+            bs = ["bw%d.%s" % (i & 1, c) for c in "xyzw"]
             for e, c in enumerate("xyzw"):
                 L.append(ind + "accx%d_%d = __builtin_amdgcn_mfma_f32_16x16x4f32(xfr[%d].%s, %s, accx%d_%d, 0, 0, 0);"
                          % (gi, e & 1, q, c, bs[e], gi, e & 1))
+    fetches = phase_fetches(pr)
+    # a wrapped product (computed at the end of step t for step t + 1) may leave its last fragments
+    # to the first window of step t + 1: the same x, more MFMAs in front of THAT hand-off
+    snap, f0, moved, KEEP = set(), None, set(), Q
     if XF:
         XW = xfold_windows(pr, [(v, pi, d) for v, pi, d, _s in XF])
         assert XW is not None
+        last_f = max(XW["win"])
+        snap = {gi for gi in XW["wrapped"] if XF[gi][1] == last_f}
+        f0 = min((f for f in XW["win"] if XW["win"][f] and fetches[f][2]), default=None)
+        if spec.xsplit and f0 is not None and f0 != last_f:
+            moved = {gi_ for gi_ in XW["win"][last_f] if gi_ in XW["wrapped"] and gi_ not in snap}
+        if moved:
+            KEEP = min(max(spec.xsplit, 1), Q)
         L.append("  const f4 zero4 = {0.f, 0.f, 0.f, 0.f};")
         L.append("  f4 xfr[%d], bw0 = zero4, bw1 = zero4;" % Q)
         L.append("  const unsigned xl_off = (unsigned)((((i64)bi * %d) + (wave * %d) * 64 + lane) * 16);" % (K * 16 // 4, Q))
         emit_xload("0", "  ")
         for gi in range(len(XF)):
             L.append("  f4 accx%d_0 = zero4, accx%d_1 = zero4;" % (gi, gi))
-            if gi in lds_of:
-                L.append("  const f4* wl%d = (const f4*)(Wl + %d) + (wave * %d) * 64 + lane;" % (gi, lds_of[gi] * K * 16, Q))
+            L.append("  const f4* wl%d = (const f4*)(Wl + %d) + (wave * %d) * 64 + lane;" % (gi, gi * K * 16, Q))
         L.append("  __syncthreads();")
         # the products the first fetching phase of step 0 needs (later steps get theirs from the
-        # last window of the step before)
-        i_wrap0 = len(L)
-        emit_xunits([(gi, q) for gi in sorted(XW["wrapped"]) for q in range(Q)], "  ")
-        i_wrap1 = len(L)
+        # last window of the step before); of the moved ones the fragments that stay
+        emit_xunits([(gi, q) for gi in sorted(XW["wrapped"]) for q in range(KEEP if gi in moved else Q)], "  ")
         if XW["ahead"] == 2:
             L.append("  if (a.T > 1) {")
             emit_xload("1", "    ")
@@ -925,16 +871,14 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     for ph in pr.phases:
         for o in ph["outs"]:
             L.append("  %s own_%d§ = %s;" % (T, o, ZERO))
-    PUBLISH = spec.init == "publish"
-    # the wait for the acknowledgement of the payload stores.  "publish" form: as an s_waitcnt the
-    # compiler's wait-count pass sees (after an inline-asm wait it still believes the x loads of the
-    # step before are pending and puts a vmcnt(0) in front of the first MFMA that reads x — where
+    # the wait for the acknowledgement of the payload stores: as an s_waitcnt the compiler's
+    # wait-count pass sees (after an inline-asm wait it still believes the x loads of the step
+    # before are pending and puts a vmcnt(0) in front of the first MFMA that reads x — where
     # only the tag store of wavefront 0 is pending: 0.3 us of skew between the wavefronts)
-    WAIT_ACK = ('    __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory");' if PUBLISH else
-                '    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");')
+    WAIT_ACK = '    __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory");'
     INIT_TAG = "(1ull << 32)"          # tags of the initial state: bit 32 set (step tags are 32-bit counts)
     prev_ops = [x for (x, kind) in keys if kind == "prev"]
-    if PUBLISH and prev_ops:
+    if prev_ops:
         # the initial state goes through the exchange like every later one: slot (0 - 1) & 3 = 3
         L.append("  if (a.T > 0) {")
         for x in prev_ops:
@@ -957,8 +901,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     L.append("  for (i64 t = 0; t < a.T; ++t) {")
     # the operand fragments are per-step values: declared here, one whose last product lies
     # before another's fetch lends it its registers (a gradient step fetches three, two at a time)
-    # (several blocks per workgroup, phases interleaved: an operand used by a later phase too must
-    # survive the other blocks' fetches in between -> its own registers per block)
+    # (several blocks per workgroup, phases interleaved: an operand used by a later phase too would
+    # have to survive the other blocks' fetches in between -> its own registers per block)
     ph_of = {}
     for pi_, ph_ in enumerate(pr.phases):
         for _a, x_ in ph_["dots"]:
@@ -966,28 +910,19 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     # measured (B = 128, H = 1024): the backward GRU kernel (every operand used by one phase)
     # gains 11 % on the training step interleaved; the forward kernel (h feeds two phases: 64 more
     # registers per block, and its early product already covered the wait) loses 5 % -> interleave
-    # only when no operand needs registers per block ("2" forces it, "0" turns it off)
-    ilv_env = str(knobs.get("SM_INTERLEAVE"))
-    ILV = NBLK > 1 and (ilv_env == "2" or (ilv_env == "1" and all(len(v_) == 1 for v_ in ph_of.values())))
-    frs = ["fr%d%s" % (ki, "§" if (ILV and len(ph_of[keys[ki]]) > 1) else "") for ki in range(len(keys))]
+    # only when no operand needs registers per block
+    ILV = NBLK > 1 and all(len(v_) == 1 for v_ in ph_of.values())
     for ki in range(len(keys)):
-        if frs[ki].endswith("§"):
-            L.extend(per_block(["    %s %s[%d];" % (VT, frs[ki], Q)]))
-        else:
-            L.append("    %s fr%d[%d];" % (VT, ki, Q))
+        L.append("    %s fr%d[%d];" % (VT, ki, Q))
     if spec.pin:
         for av, slot in sorted(pr.mats.items(), key=lambda t: t[1]):
             for s0 in range(0, spec.Ks[av] // 16, 16):
                 ops = ", ".join('"+%s"(w%d_%d)' % ("a" if spec.pin == 2 else "v", slot, s_)
                                 for s_ in range(s0, min(s0 + 16, spec.Ks[av] // 16)))
                 L.append('    asm volatile("" : %s);' % ops)
-    if spec.pin:
-        for gi in sorted(XREG):
-            for s0 in range(0, K // 16, 16):
-                ops = ", ".join('"+%s"(wx%d_%d)' % ("a" if spec.pin == 2 else "v", gi, s_)
-                                for s_ in range(s0, min(s0 + 16, K // 16)))
-                L.append('    asm volatile("" : %s);' % ops)
     i_body = len(L)              # the step body: a template, instantiated per batch block below
+    # the per-step sequence operands of the epilogue are requested behind the first fetch of the
+    # step (an HBM-cold load in front of the fetch delays every in-order wait behind it)
     nxt_loads = []
     for v in pw_seq:
         s_ = pr.seq[v]
@@ -995,15 +930,12 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         nxt_loads.append("    if (owner§ && t + 1 < a.T) nxt_%d§ = ((const %s*)a.seq[%d])[(t + 1) * a.seq_ts[%d] + "
                          "eb§ * a.seq_rs[%d] + en * a.seq_cs[%d]];" % (v, T, s_, s_, s_, s_))
     i_top = len(L)
-    if spec.nxt == "top":
-        L.extend(nxt_loads)
-        nxt_loads = []
     staged_this_step = set()
 
     def want_expr(step_expr, kind):
         """the tag a consumer of step ``step_expr``'s value waits for (initial state: INIT_TAG | base)"""
         e = "(unsigned long long)(base + (unsigned)%s + 1u)" % step_expr
-        if kind == "prev" and PUBLISH:
+        if kind == "prev":
             e = "(%s | ((unsigned long long)(t == 0) << 32))" % e
         return e
 
@@ -1033,8 +965,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         for q in range(q0, q1):
             for e, c in enumerate("xyzw"[:PV]):
                 nm = (n0, n1)[(PV * q + e) & 1]
-                L.append("      %s = %s(%s[%d].%s, w%d_%d, %s, 0, 0, 0);"
-                         % (nm, MFMA, frs[ki], q, c, slot, PV * q + e, nm))
+                L.append("      %s = %s(fr%d[%d].%s, w%d_%d, %s, 0, 0, 0);"
+                         % (nm, MFMA, ki, q, c, slot, PV * q + e, nm))
             if after_q is not None:
                 after_q(q)
         if q1 == Q:
@@ -1044,48 +976,23 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         if acc is None:
             L.append("    }")
 
-    POLLS = max(1, int(spec.polls)) if PW <= 64 else 1
-
-    def emit_spin(ind, fls, want="want64", delay=False):
+    def emit_spin(ind, fls, delay=False):
         """wait until every tag of this wavefront's producers (``fls``: one tag array per operand)
-        reads ``want``.  POLLS looks in flight: the oldest is examined while the others travel, a
-        new one replaces it — the tags are found a quarter of a round trip after they arrive, not
-        up to a whole one (r04 timeline of the gradient kernel: 2.0-2.7 us from a workgroup's own
-        tag to its loads, of which ~1.1 are the tag's way there and one look's way back)."""
+        reads ``want64``: one look at a time (64 workgroups poll each tag line)"""
         if delay and spec.spin_delay > 0:
             for _ in range(spec.spin_delay // 15):
                 L.append(ind + "__builtin_amdgcn_s_sleep(15);")
             if spec.spin_delay % 15:
                 L.append(ind + "__builtin_amdgcn_s_sleep(%d);" % (spec.spin_delay % 15))
-        if POLLS == 1:
-            L.append(ind + "for (int spin = 0;; ++spin) {")
-            L.append(ind + "  bool ok = true;")
-            for f in fls:
-                L.append(ind + "  for (int j = lane; j < %d; j += 64) ok = ok && (__hip_atomic_load(%s + j, %s) == %s);"
-                         % (PW, f, AG, want))
-            L.append(ind + "  if (__all(ok)) break;")
-            L.append(ind + "  if (spin > %d || ((spin & 255) == 255 && __hip_atomic_load(errp, %s) != 0u)) "
-                     "{ __hip_atomic_store(errp, 1u, %s); break; }" % (SPIN_LIMIT, AG, AG))
-            L.append(ind + "  __builtin_amdgcn_s_sleep(1);")
-            L.append(ind + "}")
-            return
-        L.append(ind + "{")
-        for n, f in enumerate(fls):
-            L.append(ind + "  const u64* fp%d_ = %s + (lane < %d ? lane : 0);" % (n, f, PW))
-        for d_ in range(POLLS):
-            for n in range(len(fls)):
-                L.append(ind + "  unsigned long long pl%d_%d = __hip_atomic_load(fp%d_, %s);" % (n, d_, n, AG))
-            if d_ + 1 < POLLS:
-                L.append(ind + "  __builtin_amdgcn_s_sleep(3);")
-        L.append(ind + "  for (int spin = 0;; ++spin) {")
-        L.append(ind + "    if (__all(%s)) break;" % " && ".join("pl%d_0 == %s" % (n, want) for n in range(len(fls))))
-        L.append(ind + "    if (spin > %d || ((spin & 255) == 255 && __hip_atomic_load(errp, %s) != 0u)) "
+        L.append(ind + "for (int spin = 0;; ++spin) {")
+        L.append(ind + "  bool ok = true;")
+        for f in fls:
+            L.append(ind + "  for (int j = lane; j < %d; j += 64) ok = ok && (__hip_atomic_load(%s + j, %s) == want64);"
+                     % (PW, f, AG))
+        L.append(ind + "  if (__all(ok)) break;")
+        L.append(ind + "  if (spin > %d || ((spin & 255) == 255 && __hip_atomic_load(errp, %s) != 0u)) "
                  "{ __hip_atomic_store(errp, 1u, %s); break; }" % (SPIN_LIMIT, AG, AG))
-        for n in range(len(fls)):
-            for d_ in range(POLLS - 1):
-                L.append(ind + "    pl%d_%d = pl%d_%d;" % (n, d_, n, d_ + 1))
-            L.append(ind + "    pl%d_%d = __hip_atomic_load(fp%d_, %s);" % (n, POLLS - 1, n, AG))
-        L.append(ind + "  }")
+        L.append(ind + "  __builtin_amdgcn_s_sleep(1);")
         L.append(ind + "}")
 
     def emit_fetch(pi, x, kind, bare=False):
@@ -1095,29 +1002,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         ki = keys.index((x, kind))
         src = pr.new_of_state.get(x, x)
         po_, lpp, fo_, lpf = xoff[src]
-        if kind == "prev" and PUBLISH:
-            L.append("    {")
-            step_expr = "(t - 1)"
-        elif kind == "prev":
-            k_out = pr.state[x]
-            L.append("    if (t == 0) {")
-            L.append("      const %s* ini = (const %s*)a.out[%d] + ((a.out_pos0[%d] + a.out_store[%d] - 1) %% "
-                     "a.out_store[%d]) * a.out_ts[%d] + ((i64)bi§ * 16 + r16) * a.out_rs[%d] + wave * %d + grp * %d;"
-                     % (T, T, k_out, k_out, k_out, k_out, k_out, k_out, K // 4, K // 16))
-            L.append("      const int c0 = wave * %d + grp * %d;" % (K // 4, K // 16))
-            for q in range(Q):
-                L.append("      { %s v = {%s};" % (VT, ", ".join([ZERO] * PV)))
-                L.append("        if (r16 < vrows§) { for (int e = 0; e < %d; ++e) if (c0 + %d + e < %d) v[e] = ini[%d + e]; }"
-                         % (PV, PV * q, spec.Nt, PV * q))
-                L.append("        %s[%d] = v; }" % (frs[ki], q))
-            # nothing of this path pending where the two meet: the compiler merges the two load
-            # orders into an s_waitcnt vmcnt(0) in front of the SECOND MFMA of every step
-            L.append("      __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)")
-            L.append("    } else {")
-            step_expr = "(t - 1)"
-        else:
-            L.append("    {")
-            step_expr = "t"
+        step_expr = "(t - 1)" if kind == "prev" else "t"
+        L.append("    {")
         ind = "      "
         L.append(ind + "const unsigned long long want64 = %s;" % want_expr(step_expr, kind))
         L.append(ind + "const u64* fl = a.xch + %d + (%s & 3) * %d + (i64)bi§ * %d + wave * %d;"
@@ -1127,7 +1013,7 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
                  % (po_, step_expr, lpp, 16 * K * ISZ // 8))
         for q in range(Q):
             L.append(ind + "{ const u4v g = __builtin_amdgcn_raw_buffer_load_b128(xr, ld_off + %du, so_, 16);"
-                     " %s[%d] = __builtin_bit_cast(%s, g); }" % (q * 64 * 16, frs[ki], q, VT))
+                     " fr%d[%d] = __builtin_bit_cast(%s, g); }" % (q * 64 * 16, ki, q, VT))
         L.append("    }")
 
     def emit_fetch_joint(pi, ops, bare=False):
@@ -1150,19 +1036,16 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
                      % (n, po_, lpp, 16 * K * ISZ // 8))
             for q in range(Q):
                 L.append(ind + "{ const u4v g = __builtin_amdgcn_raw_buffer_load_b128(xr, ld_off + %du, so%d_, 16);"
-                         " %s[%d] = __builtin_bit_cast(%s, g); }" % (q * 64 * 16, n, frs[ki], q, VT))
+                         " fr%d[%d] = __builtin_bit_cast(%s, g); }" % (q * 64 * 16, n, ki, q, VT))
         L.append("    }")
 
     def emit_look(pi, ind, assign=False):
         """the first look at the tags of phase pi's operand (examined after the head of the window);
         every lane loads (a clamped address): no branch, no copy the compiler would wait for"""
-        decl = "" if assign else ("const unsigned long long " if PUBLISH else "const unsigned ")
-        if PUBLISH:     # 64-bit: the low word of an initial-state tag is a step count of the launch before
-            L.append(ind + "%stg0_w%d = __hip_atomic_load(fl_w%d + (lane < %d ? lane : 0), %s);"
-                     % (decl, pi, pi, PW, AG))
-        else:
-            L.append(ind + "%stg0_w%d = __hip_atomic_load((const unsigned*)(fl_w%d + (lane < %d ? lane : 0)), %s);"
-                     % (decl, pi, pi, PW, AG))
+        decl = "" if assign else "const unsigned long long "
+        # 64-bit: the low word of an initial-state tag is a step count of the launch before
+        L.append(ind + "%stg0_w%d = __hip_atomic_load(fl_w%d + (lane < %d ? lane : 0), %s);"
+                 % (decl, pi, pi, PW, AG))
 
     def window_begin(pi, x, kind):
         """(sequence products in the loop) the first look at the tags of this phase's operand:
@@ -1172,10 +1055,7 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         po_, lpp, fo_, lpf = xoff[src]
         step_expr = "(t - 1)" if kind == "prev" else "t"
         ind = "    "
-        if PUBLISH:
-            L.append(ind + "const unsigned long long want64_w%d = %s;" % (pi, want_expr(step_expr, kind)))
-        else:
-            L.append(ind + "const unsigned want32_w%d = base + (unsigned)%s + 1u;" % (pi, step_expr))
+        L.append(ind + "const unsigned long long want64_w%d = %s;" % (pi, want_expr(step_expr, kind)))
         L.append(ind + "const u64* fl_w%d = a.xch + %d + (%s & 3) * %d + (i64)bi * %d + wave * %d;"
                  % (pi, fo_, step_expr, lpf, NJ, PW))
         L.append(ind + "const unsigned so_w%d = (unsigned)((%d + (%s & 3) * %d + (i64)bi * %d) * 8);"
@@ -1204,25 +1084,7 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         def load(q, ind2):
             L.append(ind2 + "{ const u4v g = __builtin_amdgcn_raw_buffer_load_b128(xr, ld_off, so_w%d + %du, 16);"
                      " fr%d[%d] = __builtin_bit_cast(%s, g); }" % (pi, q * 64 * 16, ki, q, VT))
-        if kind == "prev" and not PUBLISH:
-            k_out = pr.state[x]
-            L.append("    if (t == 0) {")
-            L.append("      const %s* ini = (const %s*)a.out[%d] + ((a.out_pos0[%d] + a.out_store[%d] - 1) %% "
-                     "a.out_store[%d]) * a.out_ts[%d] + ((i64)bi * 16 + r16) * a.out_rs[%d] + wave * %d + grp * %d;"
-                     % (T, T, k_out, k_out, k_out, k_out, k_out, k_out, K // 4, K // 16))
-            L.append("      const int c0 = wave * %d + grp * %d;" % (K // 4, K // 16))
-            for q in range(Q):
-                L.append("      { %s v = {%s};" % (VT, ", ".join([ZERO] * PV)))
-                L.append("        if (r16 < vrows) { for (int e = 0; e < %d; ++e) if (c0 + %d + e < %d) v[e] = ini[%d + e]; }"
-                         % (PV, PV * q, spec.Nt, PV * q))
-                L.append("        fr%d[%d] = v; }" % (ki, q))
-            emit_xunits(xunits, "      ")
-            # nothing of this path pending where the two meet: the compiler merges the two
-            # load orders into an s_waitcnt vmcnt(0) in front of the SECOND MFMA of every step
-            L.append("      __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)")
-            L.append("    } else {")
-        else:
-            L.append("    {")
+        L.append("    {")
         ind = "      "
         if pi in look_in_product:
             if pi not in look_emitted:      # the product that was to carry it was not split after all
@@ -1240,12 +1102,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         L.append(ind + "__builtin_amdgcn_sched_barrier(0);")
         if n_head or done:
             stamp("p%d window head issued" % pi)
-        if PUBLISH:
-            L.append(ind + "if (!__all(tg0_w%d == want64_w%d)) {" % (pi, pi))
-            L.append(ind + "  const unsigned long long want64 = want64_w%d;" % pi)
-        else:
-            L.append(ind + "if (!__all(tg0_w%d == want32_w%d)) {" % (pi, pi))
-            L.append(ind + "  const unsigned long long want64 = (unsigned long long)want32_w%d;" % pi)
+        L.append(ind + "if (!__all(tg0_w%d == want64_w%d)) {" % (pi, pi))
+        L.append(ind + "  const unsigned long long want64 = want64_w%d;" % pi)
         emit_spin(ind + "  ", ["fl_w%d" % pi])
         L.append(ind + "}")
         L.append(ind + "__builtin_amdgcn_sched_barrier(0);")
@@ -1264,30 +1122,12 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
         L.append("    }")
 
     pending_pub = []
-    fetches = phase_fetches(pr)
-    snap = set()
-    if XW:
-        last_f = max(XW["win"])
-        snap = {gi for gi in XW["wrapped"] if XF[gi][1] == last_f}
     # `part` is double-buffered by the running count of product phases (across steps): a phase's
     # epilogue reads never meet the next product phase's writes, and the barrier of the phase in
     # between orders everything two phases apart — no barrier between hand-off and products
     dot_phases = [pi for pi, ph in enumerate(pr.phases) if ph["dots"]]
     nph = len(pr.phases)
-    SCHED = bool(XW) and NBLK == 1 and PUBLISH
     done_early = set()          # (phase, dot) issued ahead, in front of the previous acknowledgement wait
-    reload_early = None         # the phase whose first staged-operand product carries the x loads
-    if SCHED and spec.xreload == "early" and spec.early_first:
-        nx_ = XW["reload"] + 1
-        if nx_ < nph and fetches[nx_][0] and fetches[XW["reload"]][1]:
-            reload_early = nx_
-    f0 = min((f for f in XW["win"] if XW["win"][f] and fetches[f][2]), default=None) if XW else None
-    # a wrapped product (computed at the end of step t for step t + 1) may leave its last fragments
-    # to the first window of step t + 1: the same x, more MFMAs in front of THAT hand-off
-    moved = set()
-    if SCHED and spec.xsplit and f0 is not None and f0 != last_f:
-        moved = {gi_ for gi_ in XW["win"][last_f] if gi_ in XW["wrapped"] and gi_ not in snap}
-    KEEP = min(max(spec.xsplit, 1), Q) if moved else Q
 
     def units_of(pi):
         u = []
@@ -1300,21 +1140,12 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     split_early = {}            # (phase, dot) -> fragments already issued
     look_in_product = set()     # phases whose first look is issued among that product's MFMAs
     look_emitted = set()
-    if SCHED and spec.ackfill and spec.early_first and 0 < spec.epre < Q:
+    if 0 < spec.epre < Q:
         for pi_ in range(1, nph):
             if fetches[pi_][0] and XW["win"].get(pi_) and fetches[pi_][2] and 0 < spec.elook <= Q - spec.epre:
                 look_in_product.add(pi_)
-    if moved:                   # step 0's share of the moved products: the fragments that stay
-        i_ins = len(L)
-        emit_xunits([(gi_, q) for gi_ in sorted(XW["wrapped"]) for q in range(KEEP if gi_ in moved else Q)], "  ")
-        repl = L[i_ins:]
-        del L[i_ins:]
-        shift = len(repl) - (i_wrap1 - i_wrap0)
-        L[i_wrap0:i_wrap1] = repl
-        i_body += shift
-        i_top += shift
     pre_n = 0                   # fragments of phase f0's window issued at the end of the step before
-    if SCHED and spec.xpre and f0 is not None:
+    if spec.xpre and f0 is not None:
         pre_n = min(spec.xpre, len(units_of(f0)))
         pre_units = units_of(f0)[:pre_n]
         if any(gi_ in snap for gi_, _q in pre_units):
@@ -1327,29 +1158,6 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     if NBLK == 1:
         for pi in dot_phases:
             L.append("    const int pp%d = (int)((t * %d + %d) & 1);" % (pi, len(dot_phases), dot_phases.index(pi)))
-    XLPG = 2                    # x loads behind each fragment's MFMAs of the product that carries them
-
-    xs_declared = []
-
-    def declare_xs():
-        if xs_declared:
-            return
-        xs_declared.append(1)
-        L.append("    const i64 xt_ = (t + %d < a.T) ? t + %d : a.T - 1;" % (XW["ahead"], XW["ahead"]))
-        L.append("    const __amdgpu_buffer_rsrc_t xs_ = __builtin_amdgcn_make_buffer_rsrc("
-                 "(void*)((const float*)a.seq[%d] + xt_ * a.seq_ts[%d]), 0, %du, 0x00020000);"
-                 % (spec.xfold["sx"], spec.xfold["sx"], NB * 16 * K * 4))
-
-    def xl_early(q):
-        # nothing else is in flight here: the loads issue without waiting for queue slots; all of
-        # them in the first half of the product (the rest of it covers their latency)
-        qs = range(q * XLPG, min(Q, (q + 1) * XLPG))
-        if qs:
-            L.append("      __builtin_amdgcn_sched_barrier(0);")
-            for q2 in qs:
-                L.append("      xfr[%d] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(xs_, xl_off, %du, 0));"
-                         % (q2, q2 * 64 * 16))
-            L.append("      __builtin_amdgcn_sched_barrier(0);")
     i_phase = []
     for pi, ph in enumerate(pr.phases):
         i_phase.append(len(L))
@@ -1373,27 +1181,24 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
             window_begin(pi, *fresh[0])
         early_all = early
         early = [e_ for e_ in early if (pi, e_[0]) not in done_early]
-        if pi == reload_early and len(early) == len(early_all):
-            declare_xs()
-        if spec.early_first:
-            for li, (d, a_, x) in enumerate(early):
-                if (pi, d) in split_early:          # the rest of a product begun before the hand-off
-                    def look_hook(q, pi=pi, li=li):
-                        if pi == reload_early and li == 0:      # the x loads the first part did not get to
-                            xl_early(q)
-                        if pi in look_in_product and q == split_early_q0 + spec.elook - 1:
-                            look_emitted.add(pi)
-                            L.append("      __builtin_amdgcn_sched_barrier(0);")
-                            emit_look(pi, "      ", assign=True)
-                            L.append("      __builtin_amdgcn_sched_barrier(0);")
-                    split_early_q0 = split_early[(pi, d)]
-                    emit_mfma(pi, d, a_, x, look_hook, q0=split_early_q0, acc="eacc%d_%d" % (pi, d))
-                    continue
-                emit_mfma(pi, d, a_, x, xl_early if (pi == reload_early and li == 0 and
-                                                     len(early) == len(early_all)) else None)
+        # products on operands that are already in registers run BEFORE the wait for the new
+        # operand's tags (r03 timeline, config 4 B = 64: 6.7 us per step; issuing them after the
+        # loads — to cover the load latency instead of the tag latency — measured 8.5)
+        for d, a_, x in early:
+            if (pi, d) in split_early:          # the rest of a product begun before the hand-off
+                def look_hook(q, pi=pi):
+                    if pi in look_in_product and q == split_early_q0 + spec.elook - 1:
+                        look_emitted.add(pi)
+                        L.append("      __builtin_amdgcn_sched_barrier(0);")
+                        emit_look(pi, "      ", assign=True)
+                        L.append("      __builtin_amdgcn_sched_barrier(0);")
+                split_early_q0 = split_early[(pi, d)]
+                emit_mfma(pi, d, a_, x, look_hook, q0=split_early_q0, acc="eacc%d_%d" % (pi, d))
+                continue
+            emit_mfma(pi, d, a_, x)
         # a fetch with nothing in front of it: one block per workgroup (other blocks' phases are
         # work in between), no product on staged operands issued first, no window
-        bare = NBLK == 1 and not (spec.early_first and early_all)
+        bare = NBLK == 1 and not early_all
         if not win_units and len(fresh) >= 2 and all(kind == "cur" for _x, kind in fresh):
             emit_fetch_joint(pi, fresh, bare)
             staged_this_step.update(fresh)
@@ -1406,10 +1211,9 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
                 staged_this_step.add((x, kind))
         if fresh:
             stamp("p%d tags seen, loads issued" % pi)
-            if spec.nxt == "fetch":      # behind the payload loads in the in-order queue
-                L.extend(nxt_loads)
-                nxt_loads = []
-        reload_here = bool(XW) and pi == XW["reload"] and bool(late) and reload_early is None
+            L.extend(nxt_loads)         # behind the payload loads in the in-order queue
+            nxt_loads = []
+        reload_here = bool(XW) and pi == XW["reload"] and bool(late)
         if reload_here:
             # the next x: same registers; the step index clamped (no branch); one load behind
             # each fragment's MFMAs of the first product below (issued back to back, 16 loads of
@@ -1418,10 +1222,6 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
             L.append("    const __amdgpu_buffer_rsrc_t xs_ = __builtin_amdgcn_make_buffer_rsrc("
                      "(void*)((const float*)a.seq[%d] + xt_ * a.seq_ts[%d]), 0, %du, 0x00020000);"
                      % (spec.xfold["sx"], spec.xfold["sx"], NB * 16 * K * 4))
-        if not spec.early_first:
-            # the products on operands already in registers run while the new operand is in flight
-            for d, a_, x in early:
-                emit_mfma(pi, d, a_, x)
         if early:
             stamp("p%d early products done" % pi)
         for li, (d, a_, x) in enumerate(late):
@@ -1479,27 +1279,19 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
                 L.append("      ((%s*)a.out[%d])[((a.out_pos0[%d] + t) %% a.out_store[%d]) * a.out_ts[%d] + "
                          "eb§ * a.out_rs[%d] + en] = own_%d§;" % (T, j, j, j, j, j, o))
         L.append("    }")
-        if SCHED and pub and spec.ackfill and pi + 1 < nph and spec.early_first and fetches[pi + 1][0]:
-            # products of the next phase that need nothing from this hand-off: issued while the
-            # payload stores travel (the wait below costs 0.35 us with nothing in front of it) —
-            # and in THEIR shadow the loads nobody waits for yet: the next step's epilogue operands
-            # and the next x (in front of any other wait of the step an HBM-cold load holds up the
-            # in-order queue; here it has the whole product to arrive)
-            if spec.nxt == "ack":
-                L.extend(nxt_loads)
-                nxt_loads = []
-            if pi + 1 == reload_early:
-                declare_xs()
+        if XW and pub and pi + 1 < nph and fetches[pi + 1][0]:
+            # (sequence products in the loop) products of the next phase that need nothing from
+            # this hand-off: issued while the payload stores travel (the wait below costs 0.35 us
+            # with nothing in front of it)
             for li, (d, a_, x) in enumerate(fetches[pi + 1][0]):
                 if 0 < spec.epre < Q:
                     if li == 0:     # only its first fragments here: the tag goes out sooner
                         L.append("    %s eacc%d_%d_0 = %s, eacc%d_%d_1 = %s;"
                                  % ((AT, pi + 1, d, acc_init(pi + 1, d)[0], pi + 1, d, acc_init(pi + 1, d)[1])))
-                        emit_mfma(pi + 1, d, a_, x, xl_early if pi + 1 == reload_early else None,
-                                  q0=0, q1=spec.epre, acc="eacc%d_%d" % (pi + 1, d))
+                        emit_mfma(pi + 1, d, a_, x, q0=0, q1=spec.epre, acc="eacc%d_%d" % (pi + 1, d))
                         split_early[(pi + 1, d)] = spec.epre
                     continue
-                emit_mfma(pi + 1, d, a_, x, xl_early if (pi + 1 == reload_early and li == 0) else None)
+                emit_mfma(pi + 1, d, a_, x)
                 done_early.add((pi + 1, d))
             stamp("p%d products of p%d issued" % (pi, pi + 1))
         if pre_n and pi == nph - 1:
@@ -1532,8 +1324,8 @@ def _generate_frag(spec: SpecMat, name, xoff, xtot):
     body = L[i_body:]
     del L[i_body:]
     i_for = max(i for i, l in enumerate(L) if l.startswith("  for (i64 t = 0;"))
-    if PUBLISH:     # nothing pending where the prologue meets the back edge (see WAIT_ACK)
-        L[i_for:i_for] = ["  __builtin_amdgcn_s_waitcnt(0x0F70);"]
+    # nothing pending where the prologue meets the back edge (see WAIT_ACK)
+    L[i_for:i_for] = ["  __builtin_amdgcn_s_waitcnt(0x0F70);"]
     if pre_n:
         L[i_for:i_for] = pre0_lines
     if ILV:

@@ -5,8 +5,9 @@ code objects.  For three sets of ``AESARA_HIP_*`` switches this module walks, in
 process per set (the switches are read at import), what ``prebuild.prebuild_golden_kernels`` walks
 — every golden case through ``PlanExecutor(plan, dry_run=True)``, then the full-shape pass — with
 ``device.compile_cached`` replaced by a recorder of ``sha256(source)``: nothing is compiled.  A few
-forms that no dry run selects are generated from hand-built specs.  The digests are compared with
-``tests/golden/kernel_sources.json``.
+forms that no dry run selects are generated from hand-built specs, and the forms of the persistent
+matrix-state Scan kernel that those shapes miss (``MATRIX_FORMS``) from dry runs at shapes that
+select them.  The digests are compared with ``tests/golden/kernel_sources.json``.
 
 A pull request that changes a kernel ON PURPOSE rewrites the fixture with
 
@@ -91,6 +92,82 @@ def _hand_built():
                                                                          block=1024)
 
 
+# Forms of the persistent matrix-state Scan kernel (scan_persist_mat) that neither the golden shapes
+# nor the full-shape pass select: (name, golden case, (T, B, H), switches, form) — ``form`` is
+# (exchange form, batch blocks per workgroup, sequence products in the loop, two operands fetched
+# in one polling pass) of a kernel the dry run has to generate (256 CUs in a dry run).
+MATRIX_FORMS = [
+    ("fwd_b16_h64", "cfg4_gru_b8_f32", (6, 16, 64), {}, ("frag", 1, True, False)),
+    ("fwd_b32_h512", "cfg4_gru_b8_f32", (6, 32, 512), {}, ("frag", 1, True, False)),
+    # batch slices, sequence products up front, a B = 8 remainder kernel
+    ("fwd_b200_h1024_slices", "cfg4_gru_b8_f32", (6, 200, 1024), {}, ("frag", 1, False, False)),
+    ("fwd_b32_h512_t2", "cfg4_gru_b8_f32", (2, 32, 512), {}, ("frag", 1, True, False)),
+    # gradient Scans with more 16 x 16 tiles than CUs: 2 and 4 interleaved blocks per workgroup
+    ("bptt_b128_h1024_nblk2", "gru_bptt_b4_f32", (6, 128, 1024), {}, ("frag", 2, False, True)),
+    ("bptt_b256_h1024_nblk4", "gru_bptt_b4_f32", (6, 256, 1024), {}, ("frag", 4, False, True)),
+    # ... and a forward Scan that way (h feeds two phases: its blocks run one after the other)
+    ("fwd_b128_h1024_nblk2", "cfg4_gru_b8_f32", (6, 128, 1024), {"SM_BATCH_CHUNKS": "0"},
+     ("frag", 2, False, False)),
+    # float64, four 16-byte fragments per lane and operand
+    ("bptt_f64_b16_h128", "gru_bptt_b4_f64", (6, 16, 128), {}, ("frag", 1, False, True)),
+    # weights + live fragments beyond 320 registers, blocks fit in LDS: the LDS-image form, and
+    # its joint fetch in the gradient Scan
+    ("fwd_b16_h1088_lds_image", "cfg4_gru_b8_f32", (6, 16, 1088), {}, ("flag", 1, False, False)),
+    ("bptt_b16_h1088_lds_image", "gru_bptt_b4_f32", (6, 16, 1088), {}, ("flag", 1, False, True)),
+    ("fwd_b32_h512_trace", "cfg4_gru_b8_f32", (6, 32, 512), {"SM_TRACE": "1"}, ("frag", 1, True, False)),
+    ("fwd_b5_h1088_lds_image_trace", "cfg4_gru_b8_f32", (6, 5, 1088), {"SM_TRACE": "1"},
+     ("flag", 1, False, False)),
+]
+
+
+def _matrix_forms(data, seen):
+    """{name: digest of the sources of the dry run} of MATRIX_FORMS; each run must generate a
+    matrix kernel of the form it is listed for."""
+    from aesara_amd import knobs
+    from aesara_amd import scan_persist_mat as sm
+    from aesara_amd.device import DevArray, contiguous_strides
+    from aesara_amd.exec_common import _Kernels
+    from aesara_amd.executor import PlanExecutor, _FakeBuf
+    from aesara_amd.plan import Plan
+
+    def fake(shape, dtype):
+        n = 1
+        for s in shape:
+            n *= s
+        return DevArray(_FakeBuf(n, dtype), 0, tuple(shape), contiguous_strides(shape), dtype)
+
+    generated = []
+    generate = sm.SpecMat.generate
+
+    def spy(spec):
+        joint = any(len(fresh) >= 2 and all(kind == "cur" for _x, kind in fresh)
+                    for _e, _l, fresh in sm.phase_fetches(spec.prog))
+        generated.append((spec.xmode, spec.nblk, bool(spec.xfold), joint, bool(spec.trace)))
+        return generate(spec)
+
+    sm.SpecMat.generate = spy
+    got = {}
+    try:
+        for name, case, (T, B, H), env, form in MATRIX_FORMS:
+            plan = Plan.from_json(next(c for c in data if c["name"] == case)["plan"])
+            dt = "float64" if case.endswith("f64") else "float32"
+            del seen[:], generated[:]
+            _Kernels.compiled.clear()
+            os.environ.update({"AESARA_HIP_" + k: v for k, v in env.items()})
+            try:
+                PlanExecutor(plan, dry_run=True)(fake((T, B, H), dt), fake((B, H), dt),
+                                                 *[fake((H, H), dt) for _ in range(6)])
+            finally:
+                for k in env:
+                    del os.environ["AESARA_HIP_" + k]
+            if int(knobs.get("SCAN_PERSIST")):
+                assert form + (bool(env.get("SM_TRACE")),) in generated, (name, generated)
+            got[name] = _digest(seen)
+    finally:
+        sm.SpecMat.generate = generate
+    return got
+
+
 def _collect_here():
     """Body of the child process: the switches of the set are already in the environment."""
     for p in (ROOT, os.path.join(ROOT, "oracle"), HERE):
@@ -142,7 +219,7 @@ def _collect_here():
         assert all(n in src for n in names)
         hand[name] = hashlib.sha256(src.encode()).hexdigest()[:16]
     return {"cases": cases, "raised": dict(sorted(raised.items())), "distinct": len(distinct),
-            "hand_built": hand}
+            "hand_built": hand, "matrix_forms": _matrix_forms(data, seen)}
 
 
 def collect(set_name):
@@ -161,7 +238,7 @@ def test_generated_sources_are_pinned(set_name):
         want = json.load(f)[set_name]
     got = collect(set_name)
     assert got["env"] == want["env"]
-    for part in ("cases", "hand_built"):
+    for part in ("cases", "hand_built", "matrix_forms"):
         differ = sorted(k for k in set(got[part]) | set(want[part])
                         if got[part].get(k) != want[part].get(k))
         assert not differ, "%s: generated sources changed for %s: %s" % (set_name, part, differ)

@@ -3,7 +3,7 @@
 against a plain torch loop, device time per evaluation.  The variant comes from the
 AESARA_HIP_SM_* switches in the environment (tools/sm_variants.sh runs a list of them).
 
-usage (GPU box): AESARA_HIP_SM_INIT=publish python tools/sm_ab.py [--B 64] [--trace]
+usage (GPU box): AESARA_HIP_SM_XSPLIT=8 python tools/sm_ab.py [--B 64] [--trace]
 """
 import argparse
 import json
