@@ -70,7 +70,10 @@ _RED_OPS = {"add": "add", "maximum": "maximum", "minimum": "minimum"}
 _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   "AdvancedSubtensor", "AdvancedIncSubtensor", "Reshape", "Join", "Split",
                   "CumOp", "Argmax", "MaxAndArgmax", "Sort", "ArgSort", "IfElse", "BatchedDot",
-                  "MatMul", "Ger", "RFFT", "IRFFT", "Conv2d", "Conv2dGradW", "Conv2dGradI"}
+                  "MatMul", "Ger", "RFFT", "IRFFT", "Conv2d", "Conv2dGradW", "Conv2dGradI",
+                  # (pooling could shard over its leading dimensions like an Elemwise on them; the
+                  # propagation below has no rule for "elementwise over SOME dimensions", so: replicated)
+                  "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad"}
 
 
 def _const_scalar(plan: Plan, vid: int):

@@ -878,6 +878,8 @@ def _register_handlers():
     lower_more.register(hip_lower, _static_shape, UnsupportedOp)
     from . import lower_conv
     lower_conv.register(hip_lower, _static_shape, UnsupportedOp)
+    from . import lower_pool
+    lower_pool.register(hip_lower, _static_shape, UnsupportedOp)
 
     @hip_lower.register(Scan)
     def _(op, node, ctx):

@@ -499,6 +499,32 @@ int ahip_im2col2d(int dtype, const void* x, const int64_t* x_strides, int64_t N,
 int ahip_col2im2d(int dtype, const void* col, int64_t N, int64_t C, int64_t H, int64_t W,
                   int64_t kh, int64_t kw, int64_t pad_top, int64_t pad_left, int64_t sh, int64_t sw,
                   int64_t dh, int64_t dw, int64_t OH, int64_t OW, void* out, void* stream);
+/* ---- K16: pooling ----------------------------------------------------------------------------
+ * replaces tensor/signal/pool.py:283 Pool, :1162 MaxPoolGrad, :1490 AveragePoolGrad and :1834
+ * DownsampleFactorMaxGradGrad (their c_code: the same windows in all four).  dtype: AHIP_F32 or
+ * AHIP_F64.  mode: 0 max, 1 sum, 2 average_inc_pad, 3 average_exc_pad.
+ * geo: 18 values — lead[3] (extents of up to three leading dimensions, 1 where unused), X[3] (image
+ * extents of the pooled dimensions d, h, w; 1 / window 1 / stride 1 / pad 0 in unused leading ones),
+ * O[3] (output extents), ws[3], stride[3], pad[3].  Window j of a dimension covers the image cells
+ * [max(j*stride - pad, 0), min(j*stride + ws - pad, X)); requires 0 <= pad < ws and every window to
+ * hold a cell (AHIP_EINVAL otherwise).  x is read through x_strides (6 element strides: the three
+ * leading, then the three pooled dimensions; any sign); maxout, gz, ggx and every result are
+ * contiguous: [lead][O] (z, maxout, gz, ggz) or [lead][X] (gx, ggx).
+ *   pool_fwd:         z[r]   = max / sum / average of window r; a NaN in a max window gives NaN;
+ *                     streaming != 0: x is read with non-temporal loads where a window row is one load
+ *   maxpool_grad:     gx[c]  = sum of gz[r] over the windows r holding c with maxout[r] == x[c]
+ *   avgpool_grad:     gx[c]  = sum of gz[r] / size(r) over the windows r holding c (mode 1: no division)
+ *   maxpool_gradgrad: ggz[r] = sum of ggx[c] over the cells c of window r with x[c] == maxout[r]
+ * The gradients gather per image cell in ascending window order (no atomics: a fixed order); cells
+ * under no window get 0.  Pooled extents and planes stay below 2^30; element offsets are 64-bit. */
+int ahip_pool_fwd(int dtype, int mode, int streaming, const int64_t* geo, const void* x,
+                  const int64_t* x_strides, void* z, void* stream);
+int ahip_maxpool_grad(int dtype, const int64_t* geo, const void* x, const int64_t* x_strides,
+                      const void* maxout, const void* gz, void* gx, void* stream);
+int ahip_avgpool_grad(int dtype, int mode, const int64_t* geo, const void* gz, void* gx,
+                      void* stream);
+int ahip_maxpool_gradgrad(int dtype, const int64_t* geo, const void* x, const int64_t* x_strides,
+                          const void* maxout, const void* ggx, void* ggz, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
