@@ -187,6 +187,9 @@ SIGNATURES = {
     "ahip_maxpool_grad": (i32, [i32, p_i64, vp, p_i64, vp, vp, vp, vp]),
     "ahip_avgpool_grad": (i32, [i32, i32, p_i64, vp, vp, vp]),
     "ahip_maxpool_gradgrad": (i32, [i32, p_i64, vp, p_i64, vp, vp, vp, vp]),
+    "ahip_mrg_uniform": (i32, [i32, vp, vp, i64, vp, i64, i64, vp, vp]),
+    "ahip_multinomial_from_uniform": (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
+    "ahip_choice_from_uniform": (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

@@ -73,7 +73,9 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   "MatMul", "Ger", "RFFT", "IRFFT", "Conv2d", "Conv2dGradW", "Conv2dGradI",
                   # (pooling could shard over its leading dimensions like an Elemwise on them; the
                   # propagation below has no rule for "elementwise over SOME dimensions", so: replicated)
-                  "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad"}
+                  "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad",
+                  # (every rank must draw the same numbers from the same state: replicated)
+                  "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform"}
 
 
 def _const_scalar(plan: Plan, vid: int):

@@ -196,7 +196,9 @@ def build_steps(plan: Plan, fuse: bool = True) -> List[Step]:
 _PURE_NODES = {"AllocEmpty", "Alloc", "DimShuffle", "Shape_i", "Shape", "ViewOp", "SpecifyShape",
                "Subtensor", "Reshape", "ScalarFromTensor", "TensorFromScalar", "MakeVector",
                "BroadcastTo", "DeepCopyOp", "RFFT", "IRFFT", "Conv2d", "Conv2dGradW",
-               "Conv2dGradI", "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad"}
+               "Conv2dGradI", "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad",
+               # (MrgUniform is not listed: with ``inplace`` it writes its state operand)
+               "MultinomialFromUniform", "ChoiceFromUniform"}
 
 
 def _drop_dead(plan: Plan, steps: List[Step]) -> List[Step]:

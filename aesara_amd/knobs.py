@@ -63,6 +63,10 @@ _def("GE_WAVES", 0, int, "waves per workgroup of the generated GEMM epilogue (0:
 # ---- convolution ---------------------------------------------------------------------------------
 _def("CONV_WS_MB", 256, float, "MiB of im2col workspace of a convolution (kh * kw times the image): the batch runs in "
      "chunks of as many images as fit, at least one; depends on shapes and this switch only, never on free memory")
+# ---- random streams ------------------------------------------------------------------------------
+_def("MRG_PARTS", 0, int, "pieces a stream's run of MrgUniform is cut into by jump-ahead, one lane each (bit-identical "
+     "for every value): 0 = the smallest count that puts about sixteen wavefronts on every CU, "
+     "ceil(256 * 16 * 64 / n_streams), at most one piece per sample; n = force n")
 # ---- Scan ---------------------------------------------------------------------------------------
 _def("SCAN_PERSIST", 1, int, "Scan loops as ONE persistent kernel where the class allows")
 _def("ROWS_BYTES_CAP_GB", 0.0, float, "bytes a whole-sequence evaluation of a Scan without recurrence may allocate before "

@@ -525,6 +525,36 @@ int ahip_avgpool_grad(int dtype, int mode, const int64_t* geo, const void* gz, v
                       void* stream);
 int ahip_maxpool_gradgrad(int dtype, const int64_t* geo, const void* x, const int64_t* x_strides,
                           const void* maxout, const void* ggx, void* ggz, void* stream);
+/* ---- K17: random streams ---------------------------------------------------------------------
+ * mrg_uniform replaces sandbox/rng_mrg.py:373 mrg_uniform (C body :452-537): MRG31k3p, element i of
+ * the flat sample from stream i % n_streams, in order; every bit is the reference's.  dtype (of the
+ * sample): AHIP_F32 or AHIP_F64.  rstate_in / rstate_out: contiguous int32 [n_streams][6]; every
+ * stream's final state is written to rstate_out (a stream that produced nothing keeps its state).
+ * parts >= 1: each stream's run is cut into `parts` pieces of c = ceil(ceil(n_elements / n_streams)
+ * / parts) steps, one lane each; lane p starts from the state jumped ahead p*c steps with row p of
+ * `table` (int64 [parts][18]: A1^(p*c) mod 2^31-1, then A2^(p*c) mod 2^31-21069, row-major; device
+ * memory).  parts == 1 needs no table and allows rstate_out == rstate_in; parts > 1 needs distinct
+ * state buffers.  States with words outside [0, M) are outside the generator's domain: parts == 1
+ * still steps them like the reference, a split run does not.  At most 2^31 - 1 samples.
+ * multinomial_from_uniform replaces sandbox/multinomial.py:14 MultinomialFromUniform (C body
+ * :84-161): out[n][m] = number of samples c whose first m with sum(pvals[n][0..m]) > unis[c*nb_multi
+ * + n] is m (double sum, in order, strict >); a sample no sum exceeds counts nowhere.
+ * choice_from_uniform replaces :223 ChoiceFromUniform, replace = False (C body :279-388): out[n][c]
+ * = that first m for sample c; after every sample but the last the chosen entry of the row is zeroed
+ * and the row renormalised in the dtype of pvals as :363-376 do.  pvals_copy is OVERWRITTEN: a
+ * private copy of pvals, element (n, m) at n*w_rs + m*w_cs.  A sample no sum exceeds gives 0.
+ * pdtype / udtype: AHIP_F32 or AHIP_F64; odtype: any; strides in elements; out contiguous.
+ * n_samples > nb_outcomes is AHIP_EINVAL for choice. */
+int ahip_mrg_uniform(int dtype, const void* rstate_in, void* rstate_out, int64_t n_streams,
+                     void* sample, int64_t n_elements, int64_t parts, const int64_t* table,
+                     void* stream);
+int ahip_multinomial_from_uniform(int pdtype, int udtype, int odtype, const void* pvals,
+                                  int64_t p_rs, int64_t p_cs, const void* unis, int64_t u_s,
+                                  int64_t nb_multi, int64_t nb_outcomes, int64_t n_samples,
+                                  void* out, void* stream);
+int ahip_choice_from_uniform(int pdtype, int udtype, int odtype, void* pvals_copy, int64_t w_rs,
+                             int64_t w_cs, const void* unis, int64_t u_s, int64_t nb_multi,
+                             int64_t nb_outcomes, int64_t n_samples, void* out, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
