@@ -190,6 +190,13 @@ SIGNATURES = {
     "ahip_mrg_uniform": (i32, [i32, vp, vp, i64, vp, i64, i64, vp, vp]),
     "ahip_multinomial_from_uniform": (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
     "ahip_choice_from_uniform": (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
+    "ahip_linalg_nb": (i32, []),
+    "ahip_trsm_diag": (i32, [i32, i32, i32, i64, i64, vp, i64, i64, vp, i64, i64, i64, vp, vp]),
+    "ahip_getrf_panel": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, vp, vp]),
+    "ahip_laswp": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, vp]),
+    "ahip_lu_det": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
+    "ahip_mirror_triangle": (i32, [i32, i32, i64, vp, i64, i64, vp]),
+    "ahip_check_finite": (i32, [i32, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

@@ -75,7 +75,9 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   # propagation below has no rule for "elementwise over SOME dimensions", so: replicated)
                   "Pool", "MaxPoolGrad", "AvgPoolGrad", "MaxPoolGradGrad",
                   # (every rank must draw the same numbers from the same state: replicated)
-                  "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform"}
+                  "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform",
+                  # (a factorisation couples every row and column of its matrix: not batch-splittable)
+                  "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det"}
 
 
 def _const_scalar(plan: Plan, vid: int):

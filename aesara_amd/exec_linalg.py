@@ -1,0 +1,254 @@
+"""The dense solves of a PlanExecutor: ``SolveTriangular``, ``CholeskySolve``, ``Solve``,
+``MatrixInverse`` and ``Det`` (reference: tensor/slinalg.py :280 / :130 / :365, tensor/nlinalg.py
+:100 / :196) on the kernels of csrc/linalg.hip plus ``ahip_gemm`` / ``ahip_gemv``.
+
+The block loops live here.  A triangular solve walks the diagonal in blocks of ``NB`` rows: the
+substitution on the diagonal block (``ahip_trsm_diag``), then ``X_rest -= T_rest,k X_k`` as a product
+on sub-blocks (pointer offset, the same strides, alpha = -1, beta = 1, in place).  The LU is
+right-looking: per ``NB``-wide panel the one-workgroup panel kernel, the row interchanges left and
+right of it, the unit-lower solve for ``U12`` and the product ``A22 -= L21 U12``.  Nothing reads a
+pivot or an info word on the host while a call runs, so the whole sequence records into a launch
+list; workspaces (the LU copy, the pivots) are ordinary allocations whose sizes come from the shapes,
+so the replay arena owns them.
+
+Errors.  Every node has one info word (the step's error word, ``OpsMixin._bad_ptr``); the kernels
+record a zero diagonal / pivot or a non-finite operand there and the executor raises where it
+examines error words (exec_replay.py): in the call that computed them, eager, recorded or replayed.
+
+``assume_a`` = sym / her / pos read the triangle ``lower`` names, complete the copy from it and go
+through the same LU: a ``pos`` matrix that is not positive definite is SOLVED, not refused (the one
+deliberate difference from ``scipy.linalg.solve``'s ``posv``; it keeps Cholesky out of this family).
+
+Part of :class:`aesara_amd.executor.PlanExecutor` (a mixin, like exec_pool.py)."""
+from __future__ import annotations
+
+from .exec_common import *  # noqa: F401,F403
+from .exec_common import (_I64, _VP, _i64arr, _Kernels, _FakeBuf, _CAST_SCALARS, _prod, _Arena, _os, _time)  # noqa: F401
+
+NB = 64                       # AHIP_LINALG_NB: rows of a diagonal block / columns of a panel
+INFO_TAG = 1 << 62            # AHIP_LINALG_INFO_TAG
+SINGULAR, NONFINITE = 2, 3    # AHIP_LINALG_SINGULAR / _NONFINITE
+LINALG_OPS = ("SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det")
+
+
+def is_linalg_code(code):
+    """Whether an error word holds an info code of these kernels and not a bad index of the index
+    kernels, which share the step's word (index + 1, saturated at 2^63 - 1 for a uint64 index beyond
+    int64): the tag bit alone above a kind of two bits — every other bit from 34 up is zero."""
+    return code > 0 and (code >> 34) == (INFO_TAG >> 34) and ((code >> 32) & 3) in (SINGULAR, NONFINITE)
+
+
+def linalg_error(code, opname=None):
+    """The exception an info word stands for, worded like the library the reference's ``perform``
+    calls: ``scipy.linalg.solve_triangular`` / ``solve`` / ``numpy.linalg.inv``; non-finite operands
+    as ``scipy``'s ``check_finite``."""
+    kind, k = (code >> 32) & 0xFF, 0xFFFFFFFF - (code & 0xFFFFFFFF)
+    if kind == NONFINITE:
+        return ValueError("array must not contain infs or NaNs")
+    if opname == "SolveTriangular":
+        # (trtrs reports the 1-based index; SciPy prints info - 1)
+        return np.linalg.LinAlgError(f"singular matrix: resolution failed at diagonal {k}")
+    if opname == "MatrixInverse":
+        return np.linalg.LinAlgError("Singular matrix")
+    return np.linalg.LinAlgError("Matrix is singular.")
+
+
+def _mat(a: DevArray, r0, r1, c0, c1) -> DevArray:
+    """The sub-block [r0:r1, c0:c1] of a matrix view."""
+    return a.view((r1 - r0, c1 - c0), a.strides, a.offset + r0 * a.strides[0] + c0 * a.strides[1])
+
+
+def _neutral(a: DevArray):
+    """Strides with those of extent-1 dimensions set to zero (exec_blas._gemm)."""
+    return [s if n != 1 else 0 for s, n in zip(a.strides, a.shape)]
+
+
+class LinalgMixin:
+
+    # ------------------------------------------------------------------ operands ------
+    def _la_operands(self, node, args):
+        dt = self.plan.vars[node.outputs[0]].dtype
+        ops = [self.to_device(a) for a in args]
+        if dt not in ("float32", "float64") or any(a.dtype != dt for a in ops):
+            raise TypeError(f"{node.op}: operands of dtypes {[a.dtype for a in ops]} for a {dt} result "
+                            "(one of float32 / float64 only)")
+        A = ops[0]
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError(f"{node.op}: expected a square matrix, got shape {tuple(A.shape)}")
+        if len(ops) > 1:
+            b = ops[1]
+            if b.ndim not in (1, 2) or b.shape[0] != A.shape[0]:
+                raise ValueError(f"{node.op}: shapes of a {tuple(A.shape)} and b {tuple(b.shape)} are "
+                                 "incompatible")
+        return ops, dt
+
+    def _la_info(self):
+        return _VP(self._bad_ptr())
+
+    def _la_check_finite(self, a: DevArray, info):
+        """``check_finite=True``: one pass over an operand."""
+        if a.size == 0:
+            return
+        a2 = a if a.ndim == 2 else a.view((a.shape[0], 1), (a.strides[0], 0))
+        self._launch("ahip_check_finite", (dtype_code(a.dtype), a2.shape[0], a2.shape[1], _VP(a2.ptr),
+                                           a2.strides[0], a2.strides[1], info, self._stream()))
+
+    def _la_rhs(self, b: DevArray):
+        """(a fresh contiguous copy of b: the result, solved in place; its n x m matrix view)."""
+        out = self.materialize(b)
+        return out, (out if out.ndim == 2 else out.view((out.shape[0], 1), (1, 0)))
+
+    # ------------------------------------------------------------------ products ------
+    def _la_update(self, T: DevArray, Xk: DevArray, Xr: DevArray):
+        """``Xr -= T @ Xk`` in place: ``ahip_gemv`` for one right-hand side, else ``ahip_gemm``."""
+        (M, K), m = T.shape, Xk.shape[1]
+        if M == 0 or K == 0 or m == 0:
+            return
+        dt = T.dtype
+        ct = C.c_float if dt == "float32" else C.c_double
+        alpha, beta = ct(-1.0), ct(1.0)
+        if m == 1:
+            ws_bytes = int(lib.ahip_gemv_ws_bytes(dtype_code(dt), M, K))
+            ws = self.alloc((max(ws_bytes // ITEMSIZE[dt], 1),), dt)
+            incy = Xr.strides[0] if M != 1 else 1
+            self._launch("ahip_gemv", (dtype_code(dt), M, K, C.byref(alpha), _VP(T.ptr),
+                                       T.strides[0] if M != 1 else 0, T.strides[1] if K != 1 else 1,
+                                       _VP(Xk.ptr), Xk.strides[0] if K != 1 else 1, C.byref(beta),
+                                       _VP(Xr.ptr), incy, _VP(Xr.ptr), incy, _VP(ws.ptr), ws_bytes,
+                                       self._stream()))
+            return
+        st, sx, sr = _neutral(T), _neutral(Xk), list(Xr.strides)
+        self._launch("ahip_gemm", (dtype_code(dt), M, m, K, C.byref(alpha), _VP(T.ptr), st[0], st[1],
+                                   _VP(Xk.ptr), sx[0], sx[1], C.byref(beta), _VP(Xr.ptr), sr[0], sr[1],
+                                   _VP(Xr.ptr), sr[0], sr[1], self._stream()))
+
+    # ------------------------------------------------------------------ block loops ---
+    def _la_trsm(self, T: DevArray, X: DevArray, lower, unit, info):
+        """Solve ``T X = X`` in place: ``T`` n x n triangular (any strides), ``X`` an n x m view."""
+        n, m = T.shape[0], X.shape[1]
+        if n == 0 or m == 0:
+            return
+        starts = list(range(0, n, NB))
+        for k in (starts if lower else reversed(starts)):
+            e = min(k + NB, n)
+            Tk, Xk = _mat(T, k, e, k, e), _mat(X, k, e, 0, m)
+            self._launch("ahip_trsm_diag", (dtype_code(T.dtype), int(lower), int(unit), e - k, m,
+                                            _VP(Tk.ptr), T.strides[0], T.strides[1], _VP(Xk.ptr),
+                                            X.strides[0], X.strides[1], k, info, self._stream()))
+            if lower:
+                self._la_update(_mat(T, e, n, k, e), Xk, _mat(X, e, n, 0, m))
+            else:
+                self._la_update(_mat(T, 0, k, k, e), Xk, _mat(X, 0, k, 0, m))
+
+    def _la_getrf(self, LU: DevArray, info):
+        """Right-looking blocked LU with partial pivoting of the workspace copy ``LU``, in place;
+        returns the pivots (int32 device vector).  Four launches per panel."""
+        n = LU.shape[0]
+        piv = self.alloc((n,), "int32")
+        code, (rs, cs) = dtype_code(LU.dtype), LU.strides
+        for k in range(0, n, NB):
+            e = min(k + NB, n)
+            self._launch("ahip_getrf_panel", (code, n - k, e - k, _VP(_mat(LU, k, n, k, e).ptr), rs, cs,
+                                              _VP(piv.ptr), k, info, self._stream()))
+            if n > e - k:
+                self._launch("ahip_laswp", (code, n, n - (e - k), _VP(LU.ptr), rs, cs, _VP(piv.ptr), k, e,
+                                            k, e - k, self._stream()))
+            if e < n:
+                U12 = _mat(LU, k, e, e, n)
+                self._launch("ahip_trsm_diag", (code, 1, 1, e - k, n - e, _VP(_mat(LU, k, e, k, e).ptr), rs,
+                                                cs, _VP(U12.ptr), rs, cs, k, None, self._stream()))
+                self._la_update(_mat(LU, e, n, k, e), U12, _mat(LU, e, n, e, n))
+        return piv
+
+    def _la_factor(self, A: DevArray, assume_a, lower, info):
+        """(LU, pivots) of a private copy of ``A`` — completed from the triangle ``lower`` names
+        unless ``assume_a`` is 'gen'."""
+        n = A.shape[0]
+        LU = self.alloc((n, n), A.dtype)
+        self.copy_into(LU, A)
+        if assume_a != "gen" and n > 1:
+            self._launch("ahip_mirror_triangle", (dtype_code(A.dtype), int(lower), n, _VP(LU.ptr), n, 1,
+                                                  self._stream()))
+        return LU, self._la_getrf(LU, info)
+
+    def _la_lu_solve(self, LU, piv, X):
+        n, m = LU.shape[0], X.shape[1]
+        if n == 0 or m == 0:
+            return
+        self._launch("ahip_laswp", (dtype_code(LU.dtype), n, m, _VP(X.ptr), X.strides[0], X.strides[1],
+                                    _VP(piv.ptr), 0, n, m, 0, self._stream()))
+        self._la_trsm(LU, X, True, True, None)
+        self._la_trsm(LU, X, False, False, None)       # (a zero pivot was recorded by the factorisation)
+
+    # ------------------------------------------------------------------ the Ops -------
+    def _op_SolveTriangular(self, node, args):
+        """reference: slinalg.py:301 SolveTriangular.perform (scipy.linalg.solve_triangular);
+        ``trans`` = 1 is a stride swap plus flipping ``lower``."""
+        (A, b), dt = self._la_operands(node, args)
+        p = node.params
+        info = self._la_info()
+        if p["check_finite"]:
+            self._la_check_finite(A, info)
+            self._la_check_finite(b, info)
+        lower = bool(p["lower"])
+        if p["trans"]:
+            A, lower = A.view(A.shape, (A.strides[1], A.strides[0])), not lower
+        out, X = self._la_rhs(b)
+        self._la_trsm(A, X, lower, p["unit_diagonal"], None if p["unit_diagonal"] else info)
+        return [out]
+
+    def _op_CholeskySolve(self, node, args):
+        """reference: slinalg.py:158 CholeskySolve.perform (scipy.linalg.cho_solve, LAPACK potrs:
+        two triangular solves, no singularity test)."""
+        (Cf, b), dt = self._la_operands(node, args)
+        p = node.params
+        if p["check_finite"]:
+            info = self._la_info()
+            self._la_check_finite(Cf, info)
+            self._la_check_finite(b, info)
+        Ct = Cf.view(Cf.shape, (Cf.strides[1], Cf.strides[0]))
+        out, X = self._la_rhs(b)
+        if p["lower"]:          # A = L L^T
+            self._la_trsm(Cf, X, True, False, None)
+            self._la_trsm(Ct, X, False, False, None)
+        else:                   # A = U^T U
+            self._la_trsm(Ct, X, True, False, None)
+            self._la_trsm(Cf, X, False, False, None)
+        return [out]
+
+    def _op_Solve(self, node, args):
+        """reference: slinalg.py:388 Solve.perform (scipy.linalg.solve): LU of a copy, the
+        interchanges on b, unit-lower and upper solves."""
+        (A, b), dt = self._la_operands(node, args)
+        p = node.params
+        info = self._la_info()
+        if p["check_finite"]:
+            self._la_check_finite(A, info)
+            self._la_check_finite(b, info)
+        LU, piv = self._la_factor(A, p["assume_a"], p["lower"], info)
+        out, X = self._la_rhs(b)
+        self._la_lu_solve(LU, piv, X)
+        return [out]
+
+    def _op_MatrixInverse(self, node, args):
+        """reference: nlinalg.py:124 MatrixInverse.perform (np.linalg.inv): ``Solve`` with B = I."""
+        (A,), dt = self._la_operands(node, args)
+        n = A.shape[0]
+        LU, piv = self._la_factor(A, "gen", False, self._la_info())
+        out = self.alloc((n, n), dt)
+        self.fill_zero(out)
+        if n:
+            self.copy_into(out.view((n,), (n + 1,)), self._one(dt))
+        self._la_lu_solve(LU, piv, out)
+        return [out]
+
+    def _op_Det(self, node, args):
+        """reference: nlinalg.py:210 Det.perform (np.linalg.det): the sign of the interchanges times
+        the diagonal of U; a singular matrix gives 0 (no info word), a 0 x 0 matrix 1."""
+        (A,), dt = self._la_operands(node, args)
+        n = A.shape[0]
+        LU, piv = self._la_factor(A, "gen", False, None)
+        out = self.alloc((), dt)
+        self._launch("ahip_lu_det", (dtype_code(dt), n, _VP(LU.ptr), n, 1, _VP(piv.ptr), _VP(out.ptr),
+                                     self._stream()))
+        return [out]

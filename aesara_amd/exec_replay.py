@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from .exec_common import *  # noqa: F401,F403
 from .exec_common import (_I64, _VP, _i64arr, _Kernels, _FakeBuf, _CAST_SCALARS, _prod, _Arena, _os, _time)  # noqa: F401
+from .exec_linalg import is_linalg_code, linalg_error
 
 
 class ReplayMixin:
@@ -592,8 +593,15 @@ class ReplayMixin:
     def _raise_index_error(self, codes, note=""):
         si = next(i for i, c in enumerate(codes) if c)
         code = codes[si]
-        idx = code - 1 if code > 0 else code
-        e = IndexError(f"index {idx} is out of bounds{note}")
+        if is_linalg_code(code):
+            # the info word of a dense solve (exec_linalg.py): singular matrix / non-finite operand
+            st = self.steps[si] if si < len(self.steps) else None
+            e = linalg_error(code, st.node.op if st is not None and st.kind == "node" else None)
+            if note:
+                e.args = (e.args[0] + note,)
+        else:
+            idx = code - 1 if code > 0 else code
+            e = IndexError(f"index {idx} is out of bounds{note}")
         if si < len(self.steps):
             self._annotate(e, si)
         raise e

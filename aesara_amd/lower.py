@@ -882,6 +882,8 @@ def _register_handlers():
     lower_pool.register(hip_lower, _static_shape, UnsupportedOp)
     from . import lower_rng
     lower_rng.register(hip_lower, _static_shape, UnsupportedOp)
+    from . import lower_linalg
+    lower_linalg.register(hip_lower, _static_shape, UnsupportedOp)
 
     @hip_lower.register(Scan)
     def _(op, node, ctx):

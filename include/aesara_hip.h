@@ -555,6 +555,49 @@ int ahip_multinomial_from_uniform(int pdtype, int udtype, int odtype, const void
 int ahip_choice_from_uniform(int pdtype, int udtype, int odtype, void* pvals_copy, int64_t w_rs,
                              int64_t w_cs, const void* unis, int64_t u_s, int64_t nb_multi,
                              int64_t nb_outcomes, int64_t n_samples, void* out, void* stream);
+/* ---- K18: triangular solves and LU ------------------------------------------------------------
+ * the kernels under tensor/slinalg.py:280 SolveTriangular, :130 CholeskySolve, :365 Solve and
+ * tensor/nlinalg.py:100 MatrixInverse, :196 Det (LAPACK trtrs / potrs / gesv / getrf + getri).  Only
+ * what is not a product: the caller owns the block loops and runs ahip_gemm / ahip_gemv (alpha = -1,
+ * beta = 1, Cin aliasing C) between these calls; every dependency between workgroups is a launch
+ * boundary.  dtype: AHIP_F32 or AHIP_F64.  Matrices are addressed by (row, col) element strides of
+ * any sign; extents stay below 2^30.  A block is at most AHIP_LINALG_NB (= ahip_linalg_nb()) wide.
+ * info: optional device word (uint64, zero = no error).  An error is recorded with one atomic max of
+ * AHIP_LINALG_INFO_TAG | kind << 32 | (2^32 - 1 - k): the highest kind wins and, within a kind, the
+ * smallest 0-based index k.  Kinds: AHIP_LINALG_SINGULAR (an exact zero on a referenced diagonal /
+ * a zero pivot, k = its index in the whole matrix), AHIP_LINALG_NONFINITE (k = 0).  Nothing traps,
+ * nothing divides by a zero pivot; a null info records nothing.
+ *   trsm_diag:       solves op(T) X = X in place for ONE nb x nb triangular block T (lower or upper)
+ *                    and the nb x m block X; the other triangle of T is never read, with
+ *                    unit_diagonal neither is the diagonal.  m == 1: one wave, column-oriented;
+ *                    otherwise one lane per column of X.  base: row of the block in the whole
+ *                    matrix (for info only).
+ *   getrf_panel:     LU with partial row pivoting of a rows x nb panel (rows >= nb) by ONE workgroup,
+ *                    in place (unit lower L below the diagonal, U on and above); the lowest row wins
+ *                    pivot ties.  piv[base + j] = base + (the row that changed places with row j).
+ *   laswp:           for k in [k0, k1): rows k and piv[k] of the nrows x ncols matrix B change places;
+ *                    the columns [skip0, skip0 + skiplen) are passed over (ncols counts the others).
+ *   lu_det:          out (0-d) = sign of the interchanges piv[0..n) times the product of the diagonal
+ *                    of LU, by one workgroup in a fixed order; n == 0 gives 1.
+ *   mirror_triangle: completes a symmetric matrix from its lower (lower != 0) or upper triangle.
+ *   check_finite:    records AHIP_LINALG_NONFINITE if any element of X[rows, cols] is inf or NaN. */
+#define AHIP_LINALG_NB 64
+#define AHIP_LINALG_INFO_TAG (1ull << 62)
+#define AHIP_LINALG_SINGULAR 2
+#define AHIP_LINALG_NONFINITE 3
+int ahip_linalg_nb(void);
+int ahip_trsm_diag(int dtype, int lower, int unit_diagonal, int64_t nb, int64_t m, const void* T,
+                   int64_t t_rs, int64_t t_cs, void* X, int64_t x_rs, int64_t x_cs, int64_t base,
+                   void* info, void* stream);
+int ahip_getrf_panel(int dtype, int64_t rows, int64_t nb, void* A, int64_t a_rs, int64_t a_cs,
+                     int* piv, int64_t base, void* info, void* stream);
+int ahip_laswp(int dtype, int64_t nrows, int64_t ncols, void* B, int64_t b_rs, int64_t b_cs,
+               const int* piv, int64_t k0, int64_t k1, int64_t skip0, int64_t skiplen, void* stream);
+int ahip_lu_det(int dtype, int64_t n, const void* LU, int64_t rs, int64_t cs, const int* piv,
+                void* out, void* stream);
+int ahip_mirror_triangle(int dtype, int lower, int64_t n, void* A, int64_t rs, int64_t cs, void* stream);
+int ahip_check_finite(int dtype, int64_t rows, int64_t cols, const void* X, int64_t rs, int64_t cs,
+                      void* info, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
