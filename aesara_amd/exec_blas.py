@@ -93,8 +93,7 @@ class BlasMixin:
 
     # ------------------------------------------------------------------ BLAS ----------
     def _scalar_arg(self, v, dtype):
-        val = self.host_scalar(v)
-        return C.c_float(val) if dtype == "float32" else C.c_double(val)
+        return float_scalar(dtype, self.host_scalar(v))
 
     _INT_DOT = ("bool", "int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64")
 
@@ -107,6 +106,16 @@ class BlasMixin:
             raise TypeError("BLAS operands must share one float32 / float64 dtype (Dot, BatchedDot, "
                             "MatMul: or one integer / bool dtype), got " + ", ".join(a.dtype for a in arrs))
         return dt
+
+    def _float_operands(self, node, arrays):
+        """(``arrays`` on the device, the dtype of the node's result) for the families that compute
+        in one float32 / float64 dtype throughout (convolution, pooling, the dense solves)."""
+        dt = self.plan.vars[node.outputs[0]].dtype
+        ops = [self.to_device(a) for a in arrays]
+        if dt not in ("float32", "float64") or any(a.dtype != dt for a in ops):
+            raise TypeError(f"{node.op}: operands of dtypes {[a.dtype for a in ops]} for a {dt} result "
+                            "(one of float32 / float64 only)")
+        return ops, dt
 
     def _igemm(self, A, B, batch):
         """Integer / bool product on the vector ALU (csrc/igemm.hip): NumPy's wrap-around
@@ -124,9 +133,8 @@ class BlasMixin:
         out = self.alloc((nb, M, N) if batch else (M, N), dt)
 
         def st(a):
-            s_ = [s if n != 1 else 0 for s, n in zip(a.strides, a.shape)]
-            return s_ if batch else [0] + s_
-        sa, sb, so = st(A), st(B), (list(out.strides) if batch else [0] + list(out.strides))
+            return list(a.strides) if batch else [0] + list(a.strides)
+        sa, sb, so = st(neutral_strides(A)), st(neutral_strides(B)), st(out)
         self._launch("ahip_igemm_batched", (dtype_code(dt), nb, M, N, K, _VP(A.ptr), sa[0], sa[1], sa[2],
                                             _VP(B.ptr), sb[0], sb[1], sb[2], _VP(out.ptr), so[0], so[1],
                                             so[2], self._stream()))
@@ -150,40 +158,40 @@ class BlasMixin:
         if K != K2:
             raise ValueError(f"Shape mismatch: A.shape[1] != B.shape[0] ({K} vs {K2})")
         out = self.alloc((nb, M, N) if batch else (M, N), dt)
-        a_ = C.c_float(alpha) if dt == "float32" else C.c_double(alpha)
-        b_ = C.c_float(beta) if dt == "float32" else C.c_double(beta)
         if Cin is not None and beta != 0:
             if tuple(Cin.shape[-2:]) != (M, N):
                 # z may broadcast in the reference only via explicit DimShuffle; be strict
                 raise ValueError("Gemm: z has the wrong shape")
-            cin_ptr, ci = _VP(Cin.ptr), Cin.strides
         else:
-            cin_ptr, ci = _VP(out.ptr), out.strides
-
-        def st(a):  # strides with size-1 dims neutralised
-            return [s if n != 1 else 0 for s, n in zip(a.strides, a.shape)]
-
-        sa, sb, so = st(A), st(B), out.strides
-        if batch:
-            sci = list(ci)
-            self._launch("ahip_gemm_batched", (dtype_code(dt), nb, M, N, K, C.byref(a_), _VP(A.ptr),
-                                        sa[0], sa[1], sa[2], _VP(B.ptr), sb[0], sb[1], sb[2],
-                                        C.byref(b_), cin_ptr, sci[0], sci[1], sci[2],
-                                        _VP(out.ptr), so[0], so[1], so[2], self._stream()))
+            Cin = out
+        A, B = neutral_strides(A), neutral_strides(B)
+        wsb = 0 if batch else int(lib.ahip_gemm_ws_bytes(dtype_code(dt), 1, M, N, K))
+        if wsb:
+            # few output tiles, very long K: K slices into a workspace, summed in order
+            ws = self.alloc((wsb // ITEMSIZE[dt],), dt)
+            a_, b_ = float_scalar(dt, alpha), float_scalar(dt, beta)
+            self._launch("ahip_gemm_splitk", (
+                dtype_code(dt), M, N, K, C.byref(a_), _VP(A.ptr), *A.strides, _VP(B.ptr), *B.strides,
+                C.byref(b_), _VP(Cin.ptr), *Cin.strides, _VP(out.ptr), *out.strides,
+                _VP(ws.ptr), wsb, self._stream()))
         else:
-            wsb = int(lib.ahip_gemm_ws_bytes(dtype_code(dt), 1, M, N, K))
-            if wsb:
-                # few output tiles, very long K: K slices into a workspace, summed in order
-                ws = self.alloc((wsb // ITEMSIZE[dt],), dt)
-                self._launch("ahip_gemm_splitk", (
-                    dtype_code(dt), M, N, K, C.byref(a_), _VP(A.ptr), sa[0], sa[1], _VP(B.ptr),
-                    sb[0], sb[1], C.byref(b_), cin_ptr, ci[0], ci[1], _VP(out.ptr), so[0], so[1],
-                    _VP(ws.ptr), wsb, self._stream()))
-                return out
-            self._launch("ahip_gemm", (dtype_code(dt), M, N, K, C.byref(a_), _VP(A.ptr), sa[0], sa[1],
-                                _VP(B.ptr), sb[0], sb[1], C.byref(b_), cin_ptr, ci[0], ci[1],
-                                _VP(out.ptr), so[0], so[1], self._stream()))
+            self._launch_gemm(alpha, A, B, beta, Cin, out)
         return out
+
+    def _launch_gemm(self, alpha, A, B, beta, Cin, out):
+        """``out = alpha * A @ B + beta * Cin`` on the MFMA GEMM: the one place that writes the
+        arguments of ``ahip_gemm`` (four 2-d views) and ``ahip_gemm_batched`` (four 3-d views: a
+        leading batch dimension, a zero batch stride broadcasts).  The strides go out as the views
+        carry them; nothing is allocated and split-K is the caller's choice (:meth:`_gemm`)."""
+        *nb, M, N = out.shape
+        K = A.shape[-1]
+        if len(nb) > 1 or not (A.shape == (*nb, M, K) and B.shape == (*nb, K, N) and Cin.shape == out.shape):
+            raise ValueError(f"GEMM views of shapes {A.shape} @ {B.shape} + {Cin.shape} -> {out.shape}")
+        dt = out.dtype
+        a_, b_ = float_scalar(dt, alpha), float_scalar(dt, beta)
+        self._launch("ahip_gemm_batched" if nb else "ahip_gemm", (
+            dtype_code(dt), *nb, M, N, K, C.byref(a_), _VP(A.ptr), *A.strides, _VP(B.ptr), *B.strides,
+            C.byref(b_), _VP(Cin.ptr), *Cin.strides, _VP(out.ptr), *out.strides, self._stream()))
 
     def _op_MatMul(self, node, args):
         """reference: tensor/math.py:2941 MatMul.perform (np.matmul): 1-d operands are promoted
@@ -286,22 +294,32 @@ class BlasMixin:
         if x.shape[0] != N:
             raise ValueError(f"Incompatible shapes for gemv: A {A.shape}, x {x.shape}")
         out = self.alloc((M,), dt)
-        a_ = C.c_float(alpha) if dt == "float32" else C.c_double(alpha)
-        b_ = C.c_float(beta) if dt == "float32" else C.c_double(beta)
         if y is not None and beta != 0:
             if y.shape != (M,):
                 raise ValueError("Incompatible shapes for gemv (y)")
-            yin, incy = _VP(y.ptr), (y.strides[0] if M != 1 else 1)
         else:
-            yin, incy = _VP(out.ptr), 1
-        ars = A.strides[0] if M != 1 else 0
-        acs = A.strides[1] if N != 1 else 1
+            y = out
+        self._launch_gemv(alpha, A, x, beta, y, out)
+        return out
+
+    def _launch_gemv(self, alpha, A, x, beta, yin, out):
+        """``out = alpha * A @ x + beta * yin`` (``A`` a 2-d view, the rest 1-d): the one place that
+        writes the arguments of ``ahip_gemv``, with its workspace (the only allocation) and the
+        stride conventions of extent-1 dimensions: row stride of ``A`` 0 for one row; column stride
+        of ``A`` and increment of ``x`` 1 for one column; increments of ``yin`` / ``out`` 1 for one
+        row."""
+        M, N = A.shape
+        if not (x.shape == (N,) and yin.shape == out.shape == (M,)):
+            raise ValueError(f"GEMV views of shapes {A.shape} @ {x.shape} + {yin.shape} -> {out.shape}")
+        dt = out.dtype
         ws_bytes = int(lib.ahip_gemv_ws_bytes(dtype_code(dt), M, N))
         ws = self.alloc((max(ws_bytes // ITEMSIZE[dt], 1),), dt)
-        self._launch("ahip_gemv", (dtype_code(dt), M, N, C.byref(a_), _VP(A.ptr), ars, acs, _VP(x.ptr),
-                            x.strides[0] if N != 1 else 1, C.byref(b_), yin, incy, _VP(out.ptr), 1,
-                            _VP(ws.ptr), ws_bytes, self._stream()))
-        return out
+        a_, b_ = float_scalar(dt, alpha), float_scalar(dt, beta)
+        self._launch("ahip_gemv", (
+            dtype_code(dt), M, N, C.byref(a_), _VP(A.ptr), A.strides[0] if M != 1 else 0,
+            A.strides[1] if N != 1 else 1, _VP(x.ptr), x.strides[0] if N != 1 else 1, C.byref(b_),
+            _VP(yin.ptr), yin.strides[0] if M != 1 else 1, _VP(out.ptr), out.strides[0] if M != 1 else 1,
+            _VP(ws.ptr), ws_bytes, self._stream()))
 
     def _op_Gemv(self, node, args):
         y, alpha, A, x, beta = args

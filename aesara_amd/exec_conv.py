@@ -65,11 +65,7 @@ class ConvMixin:
     CONV_PARTS_BYTES = 64 << 20     # per-image weight-gradient products held before they are summed
 
     def _conv_operands(self, node, a, b):
-        a, b = self.to_device(a), self.to_device(b)
-        dt = self.plan.vars[node.outputs[0]].dtype
-        if dt not in ("float32", "float64") or a.dtype != dt or b.dtype != dt:
-            raise TypeError(f"{node.op}: {a.dtype} and {b.dtype} operands for a {dt} result (one of "
-                            "float32 / float64 only)")
+        (a, b), dt = self._float_operands(node, (a, b))
         if a.ndim != 4 or b.ndim != 4:
             raise TypeError(f"{node.op}: operands must be 4D tensors, got {a.ndim}D and {b.ndim}D")
         return a, b, dt
@@ -82,15 +78,6 @@ class ConvMixin:
         budget = int(float(knobs.get("CONV_WS_MB")) * (1 << 20))
         return max(1, min(g.N, budget // max(slot * ITEMSIZE[dt], 1))), slot
 
-    def _conv_pack(self, src: DevArray) -> DevArray:
-        """A contiguous copy of a (possibly negatively) strided view through K8."""
-        out = self.alloc(src.shape, src.dtype)
-        if out.size:
-            self._launch("ahip_copy_strided", (dtype_code(out.dtype), out.ndim, _i64arr(out.shape),
-                                               _VP(src.ptr), _i64arr(src.strides), _VP(out.ptr),
-                                               _i64arr(out.strides), 0, self._stream()))
-        return out
-
     @staticmethod
     def _conv_flipped(k: DevArray) -> DevArray:
         s = k.strides
@@ -100,17 +87,21 @@ class ConvMixin:
     def _conv_kernel_matrix(self, kern, flip):
         """The kernel as the contiguous [O][Cg*kh*kw] matrix of the products, in correlation
         orientation (flipped when ``filter_flip``: AbstractConv.perform convolves, :2536)."""
-        if flip:
-            return self._conv_pack(self._conv_flipped(kern))
-        return kern if kern.is_contiguous() else self._conv_pack(kern)
+        if not flip and kern.is_contiguous():
+            return kern
+        src = self._conv_flipped(kern) if flip else kern
+        wm = self.alloc(src.shape, src.dtype)
+        self._copy_strided(wm, src.strides, src)
+        return wm
 
     def _conv_pixels(self, t: DevArray):
         """``t`` (N, O, OH, OW) with one element stride over its (oh, ow) pixels (a copy if the
         two spatial strides do not fold into one); returns (array, that stride)."""
         sh, st = collapse_dims(list(t.shape[2:]), [list(t.strides[2:])])
         if len(sh) != 1:
-            t = self._conv_pack(t)
-            return t, 1
+            packed = self.alloc(t.shape, t.dtype)
+            self._copy_strided(packed, t.strides, t)
+            return packed, 1
         return t, st[0][0]
 
     def _conv_cols(self, name, g, dt, x_or_out, n0, nb, col, slot):
@@ -128,10 +119,6 @@ class ConvMixin:
             else:
                 self._launch(name, (dtype_code(dt), _VP(cptr)) + geo + (_VP(ptr), self._stream()))
 
-    @staticmethod
-    def _conv_scalars(dt, *vals):
-        return [C.c_float(v) if dt == "float32" else C.c_double(v) for v in vals]
-
     def _op_Conv2d(self, node, args):
         """reference: abstract_conv.py:2501 AbstractConv.perform."""
         img, kern, dt = self._conv_operands(node, args[0], args[1])
@@ -145,18 +132,14 @@ class ConvMixin:
         wm = self._conv_kernel_matrix(kern, g.flip)
         nb, slot = self._conv_chunk(g, dt)
         col = self.alloc((nb * slot,), dt)
-        one, zero = self._conv_scalars(dt, 1.0, 0.0)
-        isz = ITEMSIZE[dt]
         for n0 in range(0, g.N, nb):
             n = min(nb, g.N - n0)
             self._conv_cols("ahip_im2col2d", g, dt, img, n0, n, col, slot)
             for grp in range(g.G):
-                y = _VP(out.ptr + ((n0 * g.O + grp * g.Og) * g.P) * isz)
-                self._launch("ahip_gemm_batched", (
-                    dtype_code(dt), n, g.Og, g.P, g.Kc, C.byref(one),
-                    _VP(wm.ptr + grp * g.Og * g.Kc * isz), 0, g.Kc, 1,
-                    _VP(col.ptr + grp * g.Kc * g.P * isz), slot, g.P, 1,
-                    C.byref(zero), y, g.O * g.P, g.P, 1, y, g.O * g.P, g.P, 1, self._stream()))
+                y = out.view((n, g.Og, g.P), (g.O * g.P, g.P, 1), out.offset + (n0 * g.O + grp * g.Og) * g.P)
+                self._launch_gemm(1.0, wm.view((n, g.Og, g.Kc), (0, g.Kc, 1), wm.offset + grp * g.Og * g.Kc),
+                                  col.view((n, g.Kc, g.P), (slot, g.P, 1), col.offset + grp * g.Kc * g.P),
+                                  0.0, y, y)
         return [out]
 
     def _op_Conv2dGradW(self, node, args):
@@ -184,16 +167,17 @@ class ConvMixin:
         dwm = self.alloc(out.shape, dt) if g.flip else out
         nb, slot = self._conv_chunk(g, dt)
         col = self.alloc((nb * slot,), dt)
-        one, zero = self._conv_scalars(dt, 1.0, 0.0)
-        isz = ITEMSIZE[dt]
         # per-image products into ``parts`` [R][O][Kc], then ONE ordered sum over the R images of a
         # group: a row of ones times ``parts`` on the same GEMM (beta = 1 from the second group on).
         # R follows from the shapes alone, so the order of the sum does not depend on the chunking.
         wsz = g.O * g.Kc
-        R = max(1, min(g.N, self.CONV_PARTS_BYTES // (wsz * isz)))
+        R = max(1, min(g.N, self.CONV_PARTS_BYTES // (wsz * ITEMSIZE[dt])))
         parts = self.alloc((R * wsz,), dt)
         ones = self.alloc((R,), dt)
+        one = float_scalar(dt, 1.0)
         self._launch("ahip_fill", (dtype_code(dt), C.byref(one), _VP(ones.ptr), R, self._stream()))
+        ts = top.strides
+        w = dwm.view((1, wsz), (wsz, 1))
         for n0 in range(0, g.N, nb):
             n = min(nb, g.N - n0)
             self._conv_cols("ahip_im2col2d", g, dt, img, n0, n, col, slot)
@@ -202,25 +186,20 @@ class ConvMixin:
                 first = (n0 + k) % R
                 m = min(n - k, R - first)
                 for grp in range(g.G):
-                    a = top.ptr + ((n0 + k) * top.strides[0] + grp * g.Og * top.strides[1]) * isz
-                    c = _VP(parts.ptr + (first * wsz + grp * g.Og * g.Kc) * isz)
-                    self._launch("ahip_gemm_batched", (
-                        dtype_code(dt), m, g.Og, g.Kc, g.P, C.byref(one),
-                        _VP(a), top.strides[0], top.strides[1], sp,
-                        _VP(col.ptr + (k * slot + grp * g.Kc * g.P) * isz), slot, 1, g.P,
-                        C.byref(zero), c, wsz, g.Kc, 1, c, wsz, g.Kc, 1, self._stream()))
+                    c = parts.view((m, g.Og, g.Kc), (wsz, g.Kc, 1), parts.offset + first * wsz + grp * g.Og * g.Kc)
+                    self._launch_gemm(
+                        1.0, top.view((m, g.Og, g.P), (ts[0], ts[1], sp),
+                                      top.offset + (n0 + k) * ts[0] + grp * g.Og * ts[1]),
+                        col.view((m, g.P, g.Kc), (slot, 1, g.P), col.offset + k * slot + grp * g.Kc * g.P),
+                        0.0, c, c)
                 k += m
                 if first + m == R or n0 + k == g.N:
-                    w = _VP(dwm.ptr)
-                    self._launch("ahip_gemm", (
-                        dtype_code(dt), 1, wsz, first + m, C.byref(one), _VP(ones.ptr), first + m, 1,
-                        _VP(parts.ptr), wsz, 1, C.byref(zero if n0 + k <= R else one), w, wsz, 1,
-                        w, wsz, 1, self._stream()))
+                    r = first + m
+                    self._launch_gemm(1.0, ones.view((1, r), (r, 1)), parts.view((r, wsz), (wsz, 1)),
+                                      0.0 if n0 + k <= R else 1.0, w, w)
         if g.flip:
-            self._launch("ahip_copy_strided", (
-                dtype_code(dt), 4, _i64arr(out.shape), _VP(self._conv_flipped(dwm).ptr),
-                _i64arr(self._conv_flipped(dwm).strides), _VP(out.ptr), _i64arr(out.strides), 0,
-                self._stream()))
+            flipped = self._conv_flipped(dwm)
+            self._copy_strided(out, flipped.strides, flipped)
         return [out]
 
     def _op_Conv2dGradI(self, node, args):
@@ -247,17 +226,14 @@ class ConvMixin:
         top, sp = self._conv_pixels(top)
         nb, slot = self._conv_chunk(g, dt)
         col = self.alloc((nb * slot,), dt)
-        one, zero = self._conv_scalars(dt, 1.0, 0.0)
-        isz = ITEMSIZE[dt]
+        ts = top.strides
         for n0 in range(0, g.N, nb):
             n = min(nb, g.N - n0)
             for grp in range(g.G):
-                c = _VP(col.ptr + grp * g.Kc * g.P * isz)
-                self._launch("ahip_gemm_batched", (
-                    dtype_code(dt), n, g.Kc, g.P, g.Og, C.byref(one),
-                    _VP(wm.ptr + grp * g.Og * g.Kc * isz), 0, 1, g.Kc,
-                    _VP(top.ptr + (n0 * top.strides[0] + grp * g.Og * top.strides[1]) * isz),
-                    top.strides[0], top.strides[1], sp,
-                    C.byref(zero), c, slot, g.P, 1, c, slot, g.P, 1, self._stream()))
+                c = col.view((n, g.Kc, g.P), (slot, g.P, 1), col.offset + grp * g.Kc * g.P)
+                self._launch_gemm(
+                    1.0, wm.view((n, g.Kc, g.Og), (0, 1, g.Kc), wm.offset + grp * g.Og * g.Kc),
+                    top.view((n, g.Og, g.P), (ts[0], ts[1], sp), top.offset + n0 * ts[0] + grp * g.Og * ts[1]),
+                    0.0, c, c)
             self._conv_cols("ahip_col2im2d", g, dt, out, n0, n, col, slot)
         return [out]

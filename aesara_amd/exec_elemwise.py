@@ -914,10 +914,18 @@ class ElemwiseMixin:
             if self._tile_plan(cshape, cstr, 1, [src.dtype, dst.dtype]) is not None:
                 self._launch_elemwise(cg.IDENTITY_SCALAR, [src], [ss], [dst], [0], list(dst.shape))
                 return
-        self._launch("ahip_copy_strided", (dtype_code(dst.dtype), max(nd, 1),
-                                    _i64arr(dst.shape or (1,)), _VP(src.ptr),
-                                    _i64arr(ss or (0,)), _VP(dst.ptr),
-                                    _i64arr(dst.strides or (0,)), int(accumulate), self._stream()))
+        self._copy_strided(dst, ss, src, accumulate)
+
+    def _copy_strided(self, dst: DevArray, src_strides, src: DevArray, accumulate=False):
+        """dst[...] (+)= ``src`` read with one of ``src_strides`` per dimension of ``dst``: the one
+        place that writes the arguments of ``ahip_copy_strided`` (K8) — always that kernel, where
+        :meth:`copy_into` may choose the tiled one."""
+        if dst.size == 0:
+            return
+        self._launch("ahip_copy_strided", (dtype_code(dst.dtype), max(dst.ndim, 1),
+                                           _i64arr(dst.shape or (1,)), _VP(src.ptr),
+                                           _i64arr(src_strides or (0,)), _VP(dst.ptr),
+                                           _i64arr(dst.strides or (0,)), int(accumulate), self._stream()))
 
     def fill_zero(self, dst: DevArray):
         """Zero a contiguous view (K7)."""

@@ -58,20 +58,16 @@ def _mat(a: DevArray, r0, r1, c0, c1) -> DevArray:
     return a.view((r1 - r0, c1 - c0), a.strides, a.offset + r0 * a.strides[0] + c0 * a.strides[1])
 
 
-def _neutral(a: DevArray):
-    """Strides with those of extent-1 dimensions set to zero (exec_blas._gemm)."""
-    return [s if n != 1 else 0 for s, n in zip(a.strides, a.shape)]
+def _column(a: DevArray) -> DevArray:
+    """The only column of an n x 1 matrix view, as a vector."""
+    return a.view(a.shape[:1], a.strides[:1])
 
 
 class LinalgMixin:
 
     # ------------------------------------------------------------------ operands ------
     def _la_operands(self, node, args):
-        dt = self.plan.vars[node.outputs[0]].dtype
-        ops = [self.to_device(a) for a in args]
-        if dt not in ("float32", "float64") or any(a.dtype != dt for a in ops):
-            raise TypeError(f"{node.op}: operands of dtypes {[a.dtype for a in ops]} for a {dt} result "
-                            "(one of float32 / float64 only)")
+        ops, dt = self._float_operands(node, args)
         A = ops[0]
         if A.ndim != 2 or A.shape[0] != A.shape[1]:
             raise ValueError(f"{node.op}: expected a square matrix, got shape {tuple(A.shape)}")
@@ -104,23 +100,12 @@ class LinalgMixin:
         (M, K), m = T.shape, Xk.shape[1]
         if M == 0 or K == 0 or m == 0:
             return
-        dt = T.dtype
-        ct = C.c_float if dt == "float32" else C.c_double
-        alpha, beta = ct(-1.0), ct(1.0)
+        # (the launchers, not _gemm / _gemv: in place, and never split-K, whose sums run in another order)
         if m == 1:
-            ws_bytes = int(lib.ahip_gemv_ws_bytes(dtype_code(dt), M, K))
-            ws = self.alloc((max(ws_bytes // ITEMSIZE[dt], 1),), dt)
-            incy = Xr.strides[0] if M != 1 else 1
-            self._launch("ahip_gemv", (dtype_code(dt), M, K, C.byref(alpha), _VP(T.ptr),
-                                       T.strides[0] if M != 1 else 0, T.strides[1] if K != 1 else 1,
-                                       _VP(Xk.ptr), Xk.strides[0] if K != 1 else 1, C.byref(beta),
-                                       _VP(Xr.ptr), incy, _VP(Xr.ptr), incy, _VP(ws.ptr), ws_bytes,
-                                       self._stream()))
-            return
-        st, sx, sr = _neutral(T), _neutral(Xk), list(Xr.strides)
-        self._launch("ahip_gemm", (dtype_code(dt), M, m, K, C.byref(alpha), _VP(T.ptr), st[0], st[1],
-                                   _VP(Xk.ptr), sx[0], sx[1], C.byref(beta), _VP(Xr.ptr), sr[0], sr[1],
-                                   _VP(Xr.ptr), sr[0], sr[1], self._stream()))
+            y = _column(Xr)
+            self._launch_gemv(-1.0, T, _column(Xk), 1.0, y, y)
+        else:
+            self._launch_gemm(-1.0, neutral_strides(T), neutral_strides(Xk), 1.0, Xr, Xr)
 
     # ------------------------------------------------------------------ block loops ---
     def _la_trsm(self, T: DevArray, X: DevArray, lower, unit, info):

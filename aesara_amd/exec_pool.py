@@ -126,30 +126,13 @@ class PoolMixin:
         p = node.params
         return pool_geometry(x.shape, ws, stride, pad, p["ndim"], p["ignore_border"], p["mode"])
 
-    def _pool_data(self, node, args):
-        dt = self.plan.vars[node.outputs[0]].dtype
-        data = [self.to_device(a) for a in args[:-3]]
-        if dt not in ("float32", "float64") or any(a.dtype != dt for a in data):
-            raise TypeError(f"{node.op}: operands of dtypes {[a.dtype for a in data]} for a {dt} result "
-                            "(one of float32 / float64 only)")
-        return data, dt
-
-    def _pool_pack(self, src: DevArray) -> DevArray:
-        """A contiguous copy of a strided view through K8."""
-        out = self.alloc(src.shape, src.dtype)
-        if out.size:
-            self._launch("ahip_copy_strided", (dtype_code(out.dtype), out.ndim, _i64arr(out.shape),
-                                               _VP(src.ptr), _i64arr(src.strides), _VP(out.ptr),
-                                               _i64arr(out.strides), 0, self._stream()))
-        return out
-
     def _pool_image(self, g, x: DevArray):
         """(x or a copy of it, its three leading extents, its six element strides): the leading
         dimensions collapsed; a copy only if more than three remain."""
         nl = len(g.lead)
         sh, st = collapse_dims(list(x.shape[:nl]), [list(x.strides[:nl])]) if nl else ([1], [[0]])
         if len(sh) > MAX_NDIM:
-            x = self._pool_pack(x)
+            x = self._pool_contig(x)        # (not contiguous: a contiguous image collapses to one)
             sh, st = collapse_dims(list(x.shape[:nl]), [list(x.strides[:nl])])
         lead3 = [1] * (3 - len(sh)) + list(sh)
         strides = [0] * (3 - len(sh)) + list(st[0]) + [0] * (MAX_NDIM - g.ndim) + list(x.strides[nl:])
@@ -159,7 +142,11 @@ class PoolMixin:
         return [1, 1, _prod(g.lead)]
 
     def _pool_contig(self, a: DevArray) -> DevArray:
-        return a if a.is_contiguous() else self._pool_pack(a)
+        if a.is_contiguous():
+            return a
+        out = self.alloc(a.shape, a.dtype)
+        self._copy_strided(out, a.strides, a)
+        return out
 
     def _pool_same_shape(self, node, what, a, want, g):
         if tuple(a.shape) != tuple(want):
@@ -176,7 +163,7 @@ class PoolMixin:
 
     def _op_Pool(self, node, args):
         """reference: pool.py:551 Pool.perform / :657 c_code."""
-        (x,), dt = self._pool_data(node, args)
+        (x,), dt = self._float_operands(node, args[:-3])
         g = self._pool_geo(node, x, args)
         out = self.alloc(g.out_shape, dt)
         if out.size == 0:
@@ -188,7 +175,7 @@ class PoolMixin:
 
     def _op_MaxPoolGrad(self, node, args):
         """reference: pool.py:1266 MaxPoolGrad.c_code."""
-        (x, maxout, gz), dt = self._pool_data(node, args)
+        (x, maxout, gz), dt = self._float_operands(node, args[:-3])
         g = self._pool_geo(node, x, args)
         self._pool_same_shape(node, "maxout", maxout, g.out_shape, g)
         self._pool_same_shape(node, "gz", gz, g.out_shape, g)
@@ -203,7 +190,7 @@ class PoolMixin:
 
     def _op_AvgPoolGrad(self, node, args):
         """reference: pool.py:1603 AveragePoolGrad.c_code; x gives its shape only."""
-        (x, gz), dt = self._pool_data(node, args)
+        (x, gz), dt = self._float_operands(node, args[:-3])
         g = self._pool_geo(node, x, args)
         if g.mode == "max":
             raise ValueError(f"{node.op}: mode 'max' has no average gradient")
@@ -221,7 +208,7 @@ class PoolMixin:
 
     def _op_MaxPoolGradGrad(self, node, args):
         """reference: pool.py:1954 DownsampleFactorMaxGradGrad.c_code."""
-        (x, maxout, ggx), dt = self._pool_data(node, args)
+        (x, maxout, ggx), dt = self._float_operands(node, args[:-3])
         g = self._pool_geo(node, x, args)
         self._pool_same_shape(node, "maxout", maxout, g.out_shape, g)
         self._pool_same_shape(node, "ggx", ggx, g.x_shape, g)

@@ -138,13 +138,13 @@ class RngMixin:
         if n_elements == 0:
             # an empty sample: unchanged state, no generator launch
             if new is not rstate:
-                self._rng_copy(rstate, new)
+                self._copy_strided(new, rstate.strides, rstate)
             return [new, sample]
         parts = mrg_parts(n_streams, n_elements, int(knobs.get("MRG_PARTS")))
         if not src.is_contiguous() or (parts > 1 and new is rstate):
             # the pieces of a stream read its old state while the last one stores the new state
             src = self.alloc(rstate.shape, "int32")
-            self._rng_copy(rstate, src)
+            self._copy_strided(src, rstate.strides, rstate)
         table = None
         if parts > 1:
             c = -(-(-(-n_elements // n_streams)) // parts)
@@ -153,13 +153,6 @@ class RngMixin:
                                           _VP(sample.ptr), n_elements, parts,
                                           _VP(table.ptr) if table is not None else _VP(), self._stream()))
         return [new, sample]
-
-    def _rng_copy(self, src: DevArray, dst: DevArray):
-        """``dst[...] = src`` through K8 (same shape; any strides)."""
-        if dst.size:
-            self._launch("ahip_copy_strided", (dtype_code(dst.dtype), dst.ndim, _i64arr(dst.shape),
-                                               _VP(src.ptr), _i64arr(src.strides), _VP(dst.ptr),
-                                               _i64arr(dst.strides), 0, self._stream()))
 
     def _multinomial_operands(self, node, args):
         """(pvals, unis, n) checked the way both C bodies check them (multinomial.py:84-99)."""
@@ -205,7 +198,7 @@ class RngMixin:
             # the private copy of pvals the lanes renormalise: stored outcome-major, so that for one
             # outcome a wavefront's rows are consecutive elements
             ws = self.alloc((nb_outcomes, nb_multi), pvals.dtype).view((nb_multi, nb_outcomes), (1, nb_multi))
-            self._rng_copy(pvals, ws)
+            self._copy_strided(ws, pvals.strides, pvals)
             self._launch("ahip_choice_from_uniform",
                          (dtype_code(pvals.dtype), dtype_code(unis.dtype), dtype_code(odt), _VP(ws.ptr),
                           ws.strides[0], ws.strides[1], _VP(unis.ptr), unis.strides[0],
