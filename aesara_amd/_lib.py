@@ -197,6 +197,9 @@ SIGNATURES = {
     "ahip_lu_det": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
     "ahip_mirror_triangle": (i32, [i32, i32, i64, vp, i64, i64, vp]),
     "ahip_check_finite": (i32, [i32, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_geqr2_panel": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
+    "ahip_larft": (i32, [i32, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
+    "ahip_qr_extract_r": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, i64, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

@@ -77,7 +77,7 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   # (every rank must draw the same numbers from the same state: replicated)
                   "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform",
                   # (a factorisation couples every row and column of its matrix: not batch-splittable)
-                  "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det"}
+                  "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det", "QR"}
 
 
 def _const_scalar(plan: Plan, vid: int):

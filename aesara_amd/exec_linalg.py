@@ -19,6 +19,16 @@ examines error words (exec_replay.py): in the call that computed them, eager, re
 through the same LU: a ``pos`` matrix that is not positive definite is SOLVED, not refused (the one
 deliberate difference from ``scipy.linalg.solve``'s ``posv``; it keeps Cholesky out of this family).
 
+``QR`` (reference: tensor/nlinalg.py:403 QRFull, ``np.linalg.qr``: LAPACK geqrf + orgqr) is blocked
+Householder on the kernels of csrc/qr.hip.  The workspace is a private copy of ``A`` held as an
+``(N, M)`` contiguous buffer and viewed as ``M x N`` with strides ``(1, M)``: the ``raw`` result without
+another copy, and contiguous columns for the one-workgroup panel kernel.  Per ``NB``-wide panel: the
+panel kernel (``tau``, and a clean copy ``V`` of the reflectors), ``G = V^T V`` and ``ahip_larft`` for the
+factor ``T`` of ``H_1 ... H_nb = I - V T V^T``, then the trailing block ``C -= V (T^T (V^T C))`` as three
+products.  Q starts as the identity and takes the panels in reverse order, ``I - V T V^T`` each, on the
+rows and columns from the panel's first on (the rest is still zero).  QR cannot fail: no info word,
+non-finite input gives non-finite output.
+
 Part of :class:`aesara_amd.executor.PlanExecutor` (a mixin, like exec_pool.py)."""
 from __future__ import annotations
 
@@ -29,6 +39,7 @@ NB = 64                       # AHIP_LINALG_NB: rows of a diagonal block / colum
 INFO_TAG = 1 << 62            # AHIP_LINALG_INFO_TAG
 SINGULAR, NONFINITE = 2, 3    # AHIP_LINALG_SINGULAR / _NONFINITE
 LINALG_OPS = ("SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det")
+QR_MODES = ("reduced", "complete", "r", "raw")
 
 
 def is_linalg_code(code):
@@ -56,6 +67,11 @@ def linalg_error(code, opname=None):
 def _mat(a: DevArray, r0, r1, c0, c1) -> DevArray:
     """The sub-block [r0:r1, c0:c1] of a matrix view."""
     return a.view((r1 - r0, c1 - c0), a.strides, a.offset + r0 * a.strides[0] + c0 * a.strides[1])
+
+
+def _t(a: DevArray) -> DevArray:
+    """The transpose of a matrix view."""
+    return a.view((a.shape[1], a.shape[0]), (a.strides[1], a.strides[0]))
 
 
 def _column(a: DevArray) -> DevArray:
@@ -237,3 +253,73 @@ class LinalgMixin:
         self._launch("ahip_lu_det", (dtype_code(dt), n, _VP(LU.ptr), n, 1, _VP(piv.ptr), _VP(out.ptr),
                                      self._stream()))
         return [out]
+
+    # ------------------------------------------------------------------ QR ------------
+    def _qr_apply(self, V: DevArray, T: DevArray, Cm: DevArray, W: DevArray, W2: DevArray):
+        """``Cm <- (I - V T V^T) Cm`` in place as three products (``W``, ``W2``: NB-row workspaces);
+        pass the transposed view of ``T`` for the transposed block reflector."""
+        nb, nc = V.shape[1], Cm.shape[1]
+        if nb == 0 or nc == 0 or V.shape[0] == 0:
+            return
+        Wv, W2v = W.view((nb, nc), (nc, 1)), W2.view((nb, nc), (nc, 1))
+        # (the launcher: in place, and never split-K, whose sums run in another order)
+        self._launch_gemm(1.0, neutral_strides(_t(V)), neutral_strides(Cm), 0.0, Wv, Wv)
+        self._launch_gemm(1.0, neutral_strides(T), neutral_strides(Wv), 0.0, W2v, W2v)
+        self._launch_gemm(-1.0, neutral_strides(V), neutral_strides(W2v), 1.0, Cm, Cm)
+
+    def _op_QR(self, node, args):
+        """reference: nlinalg.py:441 QRFull.perform (np.linalg.qr(x, mode)).  Six launches per panel
+        (panel, G, T, three products), three for a last panel that nothing follows."""
+        (A,), dt = self._float_operands(node, args)
+        mode = node.params["mode"]
+        if mode not in QR_MODES:
+            raise ValueError(f"{node.op}: mode {mode!r} (one of {', '.join(QR_MODES)})")
+        if A.ndim != 2:
+            raise ValueError(f"{node.op}: expected a matrix, got shape {tuple(A.shape)}")
+        (M, N), code = A.shape, dtype_code(dt)
+        K = min(M, N)
+        H = self.alloc((N, M), dt)
+        Aw = H.view((M, N), (1, M))
+        self.copy_into(Aw, A)
+        tau = self.alloc((K,), dt)
+        want_q = mode in ("reduced", "complete")
+        cols = M if mode == "complete" else K
+        starts = list(range(0, K, NB))
+        # the reflectors: all of them for Q, else the current panel's only
+        Vall = self.alloc((K if want_q else min(NB, K), M), dt)
+        Vall = Vall.view((M, Vall.shape[0]), (1, M))
+        Ts = self.alloc((len(starts) if want_q else 1, NB, NB), dt)
+        G = self.alloc((NB, NB), dt)
+        wide = max(N, cols) if want_q else N
+        W, W2 = self.alloc((NB, wide), dt), self.alloc((NB, wide), dt)
+        blocks = []
+        for p, k in enumerate(starts):
+            e = min(k + NB, K)
+            nb = e - k
+            V = _mat(Vall, k, M, k, e) if want_q else _mat(Vall, k, M, 0, nb)
+            T = Ts.view((nb, nb), (NB, 1), Ts.offset + (p * NB * NB if want_q else 0))
+            tau_k = _VP(tau.view((nb,), (1,), tau.offset + k).ptr)
+            self._launch("ahip_geqr2_panel", (code, M - k, nb, _VP(_mat(Aw, k, M, k, e).ptr), 1, M, tau_k,
+                                              _VP(V.ptr), V.strides[0], V.strides[1], self._stream()))
+            if e < N or want_q:
+                Gv = G.view((nb, nb), (NB, 1))
+                self._launch_gemm(1.0, neutral_strides(_t(V)), neutral_strides(V), 0.0, Gv, Gv)
+                self._launch("ahip_larft", (code, nb, _VP(Gv.ptr), NB, 1, tau_k, _VP(T.ptr), NB, 1,
+                                            self._stream()))
+                self._qr_apply(V, _t(T), _mat(Aw, k, M, e, N), W, W2)
+            blocks.append((k, V, T))
+        if mode == "raw":
+            return [H, tau]
+        R = self.alloc((M if mode == "complete" else K, N), dt)
+        if R.size:
+            self._launch("ahip_qr_extract_r", (code, R.shape[0], N, _VP(Aw.ptr), 1, M, _VP(R.ptr), N, 1,
+                                               self._stream()))
+        if not want_q:
+            return [R]
+        Q = self.alloc((M, cols), dt)
+        self.fill_zero(Q)
+        if cols:
+            self.copy_into(Q.view((cols,), (cols + 1,)), self._one(dt))
+        for k, V, T in reversed(blocks):
+            self._qr_apply(V, T, _mat(Q, k, M, k, cols), W, W2)
+        return [Q, R]

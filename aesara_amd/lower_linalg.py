@@ -7,7 +7,11 @@ Their gradients are graphs over the same Ops plus ``Dot``, ``tril`` / ``triu``, 
 (``SolveBase.L_op`` slinalg.py:244, ``SolveTriangular.L_op`` :312, ``MatrixInverse.grad``
 nlinalg.py:129, ``Det.grad`` :219), so nothing else is needed for ``aesara.grad`` through them.
 
-``Cholesky`` and the decompositions (``Eigh``, ``Eig``, ``SVD``, ``QRFull``, ``MatrixPinv``, ``Lstsq``,
+``QRFull`` (``nlinalg.qr``, nlinalg.py:403) lowers to the plan op ``QR`` with its ``mode``: two outputs
+(``Q, R`` for 'reduced' / 'complete', ``h, tau`` for 'raw') or one ('r').  The Op has no ``grad``, so
+neither has the lowering (csrc/qr.hip; executor: exec_linalg.py).
+
+``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``MatrixPinv``, ``Lstsq``,
 ``Eigvalsh``, ``Expm``, the Lyapunov solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they
 are refused by name like every Op without one.
 
@@ -18,6 +22,7 @@ from .plan import Node
 
 FLOATS = ("float32", "float64")
 ASSUME_A = ("gen", "sym", "her", "pos")
+QR_MODES = ("reduced", "complete", "r", "raw")
 _TRANS = {0: 0, 1: 1, 2: 1, "N": 0, "T": 1, "C": 1}
 
 
@@ -28,7 +33,7 @@ def family(name):
 
 
 def register(hip_lower, static_shape, UnsupportedOp):                       # noqa: N803
-    from aesara.tensor.nlinalg import Det, MatrixInverse
+    from aesara.tensor.nlinalg import Det, MatrixInverse, QRFull
     from aesara.tensor.slinalg import CholeskySolve, Solve, SolveTriangular
 
     from .lower_more import _B
@@ -83,3 +88,12 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
     def _(op, node, ctx):
         # reference: nlinalg.py:196 Det (perform :210 np.linalg.det(x) in x's dtype)
         _emit("Det", node, ctx, {})
+
+    @hip_lower.register(QRFull)
+    def _(op, node, ctx):
+        # reference: nlinalg.py:403 QRFull (perform :441 np.linalg.qr(x, mode); make_node :418 declares
+        # float outputs of the operand's item size, so an integer operand is refused by _emit)
+        if op.mode not in QR_MODES:
+            raise UnsupportedOp(f"{family('QRFull')} for mode = {op.mode!r} (one of "
+                                f"{', '.join(QR_MODES)})")
+        _emit("QR", node, ctx, {"mode": str(op.mode)})

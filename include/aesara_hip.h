@@ -598,6 +598,27 @@ int ahip_lu_det(int dtype, int64_t n, const void* LU, int64_t rs, int64_t cs, co
 int ahip_mirror_triangle(int dtype, int lower, int64_t n, void* A, int64_t rs, int64_t cs, void* stream);
 int ahip_check_finite(int dtype, int64_t rows, int64_t cols, const void* X, int64_t rs, int64_t cs,
                       void* info, void* stream);
+/* ---- K19: Householder QR ----------------------------------------------------------------------
+ * the kernels under tensor/nlinalg.py:403 QRFull (np.linalg.qr: LAPACK geqrf + orgqr).  As for K18
+ * only what is not a product: the caller owns the panel loop and applies a block reflector
+ * H_1 ... H_nb = I - V T V^T with three ahip_gemm calls.  dtype: AHIP_F32 or AHIP_F64; (row, col)
+ * element strides; extents below 2^30; a panel is at most AHIP_LINALG_NB wide.  Nothing fails, so
+ * there is no info word; every fold has a fixed order (no float atomics).
+ *   geqr2_panel:  factors a rows x nb panel (rows >= nb) in place by ONE workgroup: R on and above the
+ *                 diagonal, the reflectors below it, LAPACK larfg's convention (a zero column below
+ *                 the diagonal: tau = 0, r_jj unchanged; else beta = -sign(alpha) hypot(alpha, ||x||),
+ *                 tau = (beta - alpha) / beta, v = x / (alpha - beta), r_jj = beta; the norm is
+ *                 max-scaled).  Writes tau[0:nb] and V (rows x nb): the reflectors with ones on the
+ *                 diagonal and exact zeros above it.
+ *   larft:        T (nb x nb upper triangular, exact zeros below the diagonal) of the compact WY form
+ *                 from G = V^T V (only its strict upper triangle is read) and tau, by one wave.
+ *   qr_extract_r: R[rows, cols] = the upper trapezoid of A, exact zeros below the diagonal. */
+int ahip_geqr2_panel(int dtype, int64_t rows, int64_t nb, void* A, int64_t a_rs, int64_t a_cs, void* tau,
+                     void* V, int64_t v_rs, int64_t v_cs, void* stream);
+int ahip_larft(int dtype, int64_t nb, const void* G, int64_t g_rs, int64_t g_cs, const void* tau, void* T,
+               int64_t t_rs, int64_t t_cs, void* stream);
+int ahip_qr_extract_r(int dtype, int64_t rows, int64_t cols, const void* A, int64_t a_rs, int64_t a_cs,
+                      void* R, int64_t r_rs, int64_t r_cs, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
