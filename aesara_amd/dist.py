@@ -81,10 +81,8 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
 
 
 def _const_scalar(plan: Plan, vid: int):
-    v = plan.vars[vid]
-    if v.const is not None and len(v.const.get("data", ())) == 1:
-        return float(v.const["data"][0])
-    return None
+    c = plan.const_scalar(vid)
+    return None if c is None else float(c)
 
 
 def _ident_scalar(n_in=1):

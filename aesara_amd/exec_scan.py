@@ -22,7 +22,7 @@ class ScanMixin:
         if self.fuse and p.get("sit_sot_in_slices") and not p.get("as_while"):
             # a weight gradient summed inside the loop (sit-sot Gemm / Ger accumulator) whose
             # buffer holds ONE row: the loop without it + one product over the stacked operands
-            # behind it (fusion.push_out_product_accumulators, applied to this node alone; the
+            # behind it (scan_rewrite.push_out_product_accumulators, applied to this node alone; the
             # buffer length is known only now)
             alt = self._inner.get(("sunk", key))
             if alt is None:
@@ -59,7 +59,7 @@ class ScanMixin:
                 p.get("as_while") or p.get("n_shared_outs", 0) or p.get("mit_mot_in_slices")
                 or p["mit_sot_in_slices"] or p["sit_sot_in_slices"]):
             # no recurrence at all (aesara.map, the row loops of jacobian / hessian / Rop): the step
-            # restated over whole sequences, evaluated ONCE (fusion.batch_map_step)
+            # restated over whole sequences, evaluated ONCE (scan_rewrite.batch_map_step)
             rows = self._inner.get(("rows", key))
             if rows is None:
                 r = batch_map_step(inner_plan, p["n_seqs"])

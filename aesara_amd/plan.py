@@ -169,7 +169,22 @@ class Plan:
     def loads(s):
         return Plan.from_json(json.loads(s))
 
+    def copy(self, name=None, nodes=None):
+        """Shallow copy: own var table and lists (``nodes`` instead of this plan's), shared Var / Node objects."""
+        return Plan(name or self.name, dict(self.vars), list(self.inputs), list(self.outputs),
+                    list(self.nodes if nodes is None else nodes))
+
     # ---- queries ----------------------------------------------------------------
+    def producers(self):
+        """var id -> the node that computes it"""
+        return {o: n for n in self.nodes for o in n.outputs}
+
+    def const_scalar(self, vid):
+        """The Python scalar of a size-1 constant held as ``"data"``; None for every other variable
+        (callers apply ``int`` / ``float`` and their own dtype test)."""
+        c = self.vars[vid].const
+        return c["data"][0] if c is not None and len(c.get("data", ())) == 1 else None
+
     def clients(self):
         """var id -> list of (node index, input position); outputs counted as client 'out'."""
         c: Dict[int, list] = {vid: [] for vid in self.vars}

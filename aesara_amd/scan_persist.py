@@ -154,8 +154,8 @@ class _RowDot:
 
 
 def _const1(plan, vid):
-    v = plan.vars[vid]
-    return v.const is not None and len(v.const.get("data", ())) == 1 and float(v.const["data"][0]) == 1.0
+    c = plan.const_scalar(vid)
+    return c is not None and float(c) == 1.0
 
 
 RED_BASE = 1 << 20          # id of the vector a reduction folds: RED_BASE + its 0-d result's id

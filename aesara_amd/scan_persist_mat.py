@@ -198,7 +198,7 @@ class SpecMat:
 
 def xfold_pairs(prog, lifted_outs):
     """In-kernel sequence products (round 3).  ``lifted_outs``: loop-plan variables that are rows of
-    whole-sequence products ``x_t @ W_k`` (what ``fusion.hoist_sequence_only`` lifted out).  The
+    whole-sequence products ``x_t @ W_k`` (what ``scan_rewrite.hoist_sequence_only`` lifted out).  The
     product can move INTO the persistent loop — accumulated on the matrix cores by the same
     wavefronts, in the shadow of the hand-off latency, feeding the accumulator of the recurrent
     product it is added to — when the step uses it in exactly one place: ``dot_d + v`` (possibly

@@ -1027,7 +1027,7 @@ def _():
 def _():
     """An RNN whose step looks its input up itself — ``E[idx_t]`` by the step's index (a vector
     state) — plus a step that builds ``one_hot(idx_t)`` with set_subtensor: index glue on sequence
-    rows inside a recurrent step (fusion.push_out_sequence_glue restates it over whole sequences
+    rows inside a recurrent step (scan_rewrite.push_out_sequence_glue restates it over whole sequences
     in front of the Scan; the loop that is left is the plain ``tanh(x_t + h U)`` recurrence)."""
     idx, E, U, h0 = at.lvector("idx"), at.dmatrix("E"), at.dmatrix("U"), at.dvector("h0")
 
@@ -1071,7 +1071,7 @@ def _():
 @case("scan_map_jacobian_rows", rtol=1e-12, atol=1e-12)
 def _():
     """``gradient.jacobian`` (gradient.py:1930): a Scan over ``arange(n)`` with no recurrence whose
-    step takes row i of the gradient — the all-rows restatement (fusion.batch_map_step)."""
+    step takes row i of the gradient — the all-rows restatement (scan_rewrite.batch_map_step)."""
     x, W = at.dvector("x"), at.dmatrix("W")
     y = at.tanh(at.dot(W, x)) * x.sum()
     return [x, W], [ae.gradient.jacobian(y, x)], [N((5,), seed=1), N((5, 5), seed=2, scale=0.5)]

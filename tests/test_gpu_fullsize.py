@@ -593,7 +593,7 @@ def test_gru_bptt_against_torch_autograd(T, H, B, name):
 
 def test_biased_rnn_bptt_against_torch_autograd():
     """A batched tanh RNN with a bias under aesara.grad at a real shape: the bias accumulator is
-    rebuilt after the loop (fusion.push_out_accumulators), both Scans run persistent; loss and the
+    rebuilt after the loop (scan_rewrite.push_out_accumulators), both Scans run persistent; loss and the
     gradients wrt W, U, b, h0 against torch.autograd of an fp64 restatement."""
     import torch
     from aesara_amd.executor import PlanExecutor

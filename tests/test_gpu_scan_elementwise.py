@@ -51,7 +51,7 @@ def test_elementwise_scans_run_as_one_launch_and_match(name, use_graph):
 def test_scans_without_recurrence_are_one_evaluation_over_whole_sequences(name, use_graph):
     """aesara.map / the row loops of gradient.jacobian and gradient.hessian (scan/basic.py:71 without
     outputs_info; gradient.py:1930, :2027): no step reads what another wrote, so the step plan is
-    restated over whole sequences (fusion.batch_map_step) and evaluated once — results = the
+    restated over whole sequences (scan_rewrite.batch_map_step) and evaluated once — results = the
     reference's outputs = the launch-list path (to the goldens' tolerance: a Gemv per step there,
     one GEMM here)."""
     from aesara_amd import executor as E

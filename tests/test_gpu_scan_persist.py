@@ -57,7 +57,7 @@ def test_two_tap_bptt_runs_persistent(name, use_graph):
     buffer: out-tap j of step i is tap j - 1 of step i + 1; scan/op.py:2379) and it accumulates
     the weight gradient inside the loop (a sit-sot Gemm / Ger per step that the reference's
     PushOutDot1 lifts for one tap only) — now ONE product over the stacked operands behind the
-    loop (fusion.push_out_product_accumulators, decided per call: the buffer holds one row).
+    loop (scan_rewrite.push_out_product_accumulators, decided per call: the buffer holds one row).
     Forward and gradient Scan both persistent; results = the reference's, = the launch-list path
     to summation order."""
     from aesara_amd import executor as E
@@ -450,7 +450,7 @@ def test_sgd_loop_over_bptt_plan_replay_equals_eager(batch):
 @pytest.mark.parametrize("T,B,D", [(48, 64, 96), (7, 5, 20)])
 def test_fused_gate_lstm_runs_persistent(T, B, D):
     """The usual LSTM step — one product for the four gates, sliced by columns — is split per gate
-    (fusion.split_column_slices: column views of W / U / b) and runs as the matrix-state persistent
+    (scan_rewrite.split_column_slices: column views of W / U / b) and runs as the matrix-state persistent
     kernel with ONE hand-off per step (h; the cell state stays in the element owners' registers).
     Every hidden state and the last cell state against an fp64 restatement."""
     import torch
@@ -816,7 +816,7 @@ def test_vector_state_do_while_trip_counts(scale):
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_embedding_lookup_inside_the_step_leaves_the_loop(use_graph):
     """``E[idx_t]`` inside a recurrent step (scalar index, vector state; index vector, float32 matrix
-    state) is restated over whole sequences in front of the Scan (fusion.push_out_sequence_glue): the
+    state) is restated over whole sequences in front of the Scan (scan_rewrite.push_out_sequence_glue): the
     forward loops run on the persistent kernels, results = the reference's, and at T = 300 with a
     10^4-row table = NumPy."""
     import torch

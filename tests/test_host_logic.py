@@ -298,7 +298,7 @@ def test_device_filter_type_decisions():
 
 @pytest.mark.parametrize("name", ["scan_embedding_lookup_in_step", "scan_embedding_lookup_batch_f32"])
 def test_index_glue_on_sequence_rows_leaves_the_step(name):
-    """fusion.push_out_sequence_glue: ``E[idx_t]`` (scalar index / index vector of a batch) and the
+    """scan_rewrite.push_out_sequence_glue: ``E[idx_t]`` (scalar index / index vector of a batch) and the
     ``set_subtensor(zeros[k_t], 1)`` unit vectors of a recurrent step are restated over whole
     sequences in front of the Scan and enter it as sequences; the rewritten plan gives the
     REFERENCE's outputs (oracle), the forward step has no index node left, and the dry run puts the
@@ -306,7 +306,7 @@ def test_index_glue_on_sequence_rows_leaves_the_step(name):
     import interp
     from golden_util import CASES, assert_matches, case_expected, case_inputs, case_plan
     from aesara_amd.executor import PlanExecutor
-    from aesara_amd.fusion import push_out_sequence_glue
+    from aesara_amd.scan_rewrite import push_out_sequence_glue
     c = next(c for c in CASES if c["name"] == name)
     plan = case_plan(c)
     p2 = push_out_sequence_glue(plan)
@@ -323,7 +323,7 @@ def test_index_glue_on_sequence_rows_leaves_the_step(name):
     # gradient) leaves ITS loop as one scatter-add behind it (push_out_product_accumulators, the
     # two-row buffer form: [acc_{T-1}, acc_T]); the plan with every Scan in that form still gives
     # the reference's outputs
-    from aesara_amd.fusion import push_out_product_accumulators, read_last_row_only, zero_filled_vars
+    from aesara_amd.scan_rewrite import push_out_product_accumulators, read_last_row_only, zero_filled_vars
     from aesara_amd.plan import Node, Plan
     zeros, last = zero_filled_vars(p2), read_last_row_only(p2)
     nodes, ren, vars_, sunk = [], {}, dict(p2.vars), 0
@@ -356,14 +356,14 @@ def test_index_glue_on_sequence_rows_leaves_the_step(name):
 @pytest.mark.parametrize("name", ["scan_nitsot_map", "scan_map_jacobian_rows", "scan_map_hessian_unit_vectors",
                                   "scan_map_rows_reduce_broadcast"])
 def test_scans_without_recurrence_restated_over_whole_sequences(name):
-    """fusion.batch_map_step: every Scan without recurrence of these goldens is replaced by ONE
+    """scan_rewrite.batch_map_step: every Scan without recurrence of these goldens is replaced by ONE
     evaluation of the restated step plan over whole sequences (host logic of
     ``ScanMixin._scan_all_rows`` restated in NumPy: first n_steps rows in, last ``keep`` rows out) —
     the outputs must still be the REFERENCE's (tests/golden), all through the oracle."""
     import copy
     import interp
     from golden_util import CASES, assert_matches, case_expected, case_inputs, case_plan
-    from aesara_amd.fusion import batch_map_step
+    from aesara_amd.scan_rewrite import batch_map_step
     from aesara_amd.plan import Node
     c = next(c for c in CASES if c["name"] == name)
     plan = copy.copy(case_plan(c))
@@ -395,12 +395,12 @@ def test_scans_without_recurrence_restated_over_whole_sequences(name):
 
 @pytest.mark.parametrize("name", ["gru_bptt_b1_f32", "gru_bptt_b4_f32", "lstm_bptt_vec_f32", "cfg4_gru_b1_f32"])
 def test_sequence_only_hoisting_preserves_the_step(name):
-    """fusion.hoist_sequence_only on the Scan inner plans of the golden recurrences and their
+    """scan_rewrite.hoist_sequence_only on the Scan inner plans of the golden recurrences and their
     gradient Scans: the lifted plan evaluated ONCE over whole sequences plus the reduced step plan
     must give, for every step, what the original step plan gives (all three through the oracle)."""
     import interp
     from golden_util import CASES, case_plan
-    from aesara_amd.fusion import hoist_sequence_only, split_invariant
+    from aesara_amd.scan_rewrite import hoist_sequence_only, split_invariant
     plan = case_plan(next(c for c in CASES if c["name"] == name))
     rng = np.random.default_rng(5)
     T, B, H = 6, 3, 8
@@ -449,12 +449,12 @@ def test_sequence_only_hoisting_preserves_the_step(name):
 @pytest.mark.parametrize("name", ["lstm_bptt_float32", "lstm_fused_fwd_f32", "lstm_bptt_float64",
                                   "lstm_fused_vec_f32"])
 def test_column_slice_splitting_preserves_the_step(name):
-    """fusion.split_column_slices on fused-gate LSTM steps (forward and gradient inner plans): the
+    """scan_rewrite.split_column_slices on fused-gate LSTM steps (forward and gradient inner plans): the
     rewritten step (one product chain per gate, column views of the invariant operands) gives the
     same outputs as the original one, through the oracle; the forward step must actually change."""
     import interp
     from golden_util import CASES, case_plan
-    from aesara_amd.fusion import split_column_slices
+    from aesara_amd.scan_rewrite import split_column_slices
     plan = case_plan(next(c for c in CASES if c["name"] == name))
     changed = 0
     for node in plan.nodes:
@@ -481,13 +481,13 @@ def test_column_slice_splitting_preserves_the_step(name):
 
 
 def test_accumulator_push_out_preserves_every_golden_scan_plan():
-    """fusion.push_out_accumulators on every golden plan with a Scan: where a sit-sot accumulator
+    """scan_rewrite.push_out_accumulators on every golden plan with a Scan: where a sit-sot accumulator
     (bias gradients of batched recurrences, summed inside the gradient Scan) is rebuilt after the
     loop, the rewritten plan gives the same outputs through the oracle — whatever row of the
     accumulator buffer the outer graph reads."""
     import interp
     from golden_util import CASES, case_inputs, case_plan
-    from aesara_amd.fusion import push_out_accumulators
+    from aesara_amd.scan_rewrite import push_out_accumulators
     changed = []
     for c in CASES:
         plan = case_plan(c)
@@ -507,12 +507,12 @@ def test_accumulator_push_out_preserves_every_golden_scan_plan():
 @pytest.mark.parametrize("name", ["lstm_fused_bptt_h64_f32", "lstm_bptt_float32", "lstm_bptt_float64",
                                   "lstm_fused_vec_bptt_f32"])
 def test_assembled_gate_gradients_leave_the_step(name):
-    """fusion.split_assembled_columns (after push_out_accumulators) on fused-gate LSTM gradient
+    """scan_rewrite.split_assembled_columns (after push_out_accumulators) on fused-gate LSTM gradient
     Scans: the 4H-wide assembled gate gradient becomes per-gate nit-sot outputs + one Join after the
     loop, its product a sum over row blocks of the weight matrix — same outputs through the oracle."""
     import interp
     from golden_util import CASES, case_inputs, case_plan
-    from aesara_amd.fusion import push_out_accumulators, split_assembled_columns
+    from aesara_amd.scan_rewrite import push_out_accumulators, split_assembled_columns
     c = next(c for c in CASES if c["name"] == name)
     plan, ins = case_plan(c), case_inputs(c)
     p1 = push_out_accumulators(plan)
@@ -532,7 +532,7 @@ def test_column_slice_splitting_keeps_broadcast_operands_whole():
     leave that operand unsliced (it has no columns a:b) — it used to be cut to an empty [1, 0]
     array for every gate with a >= 1."""
     import interp
-    from aesara_amd.fusion import split_column_slices
+    from aesara_amd.scan_rewrite import split_column_slices
     from aesara_amd.plan import Node, Plan
     p = Plan("bcast_gate", {}, [], [], [])
     h = p.new_var("float64", [None, None], "h")          # [B, H]
@@ -581,7 +581,7 @@ def test_accumulator_push_out_with_a_buffer_longer_than_the_loop():
     import copy
     import interp
     from golden_util import CASES, case_inputs, case_plan
-    from aesara_amd.fusion import push_out_accumulators
+    from aesara_amd.scan_rewrite import push_out_accumulators
     from aesara_amd.plan import Node
     c = next(c for c in CASES if c["name"] == "rnn_bias_bptt_b4_f32")
     plan = copy.deepcopy(case_plan(c))
@@ -620,10 +620,10 @@ def test_accumulator_push_out_with_a_buffer_longer_than_the_loop():
 
 
 def test_shared_left_dots_become_one_wide_product():
-    """fusion.merge_shared_left_dots: three ``Dot22(x, W_k)`` of one operand -> one product against
+    """scan_rewrite.merge_shared_left_dots: three ``Dot22(x, W_k)`` of one operand -> one product against
     the joined weights + column views; same values through the oracle, other nodes untouched."""
     import interp
-    from aesara_amd.fusion import merge_shared_left_dots
+    from aesara_amd.scan_rewrite import merge_shared_left_dots
     from aesara_amd.plan import Node, Plan
     p = Plan("gates", {}, [], [], [])
     x = p.new_var("float64", [None, None], "x")
@@ -705,7 +705,7 @@ _PRODUCT_ACC = ["sp_taps_bptt_f64", "sm_taps_bptt_b16_f32", "scan_variant_1", "s
 
 @pytest.mark.parametrize("name", _PRODUCT_ACC)
 def test_product_accumulators_leave_the_loop_as_one_product(name):
-    """fusion.push_out_product_accumulators (what PushOutDot1 of the reference, scan/rewriting.py,
+    """scan_rewrite.push_out_product_accumulators (what PushOutDot1 of the reference, scan/rewriting.py,
     does for the one-tap gradient only): the weight gradient a gradient Scan sums inside its loop —
     a sit-sot ``Gemm(acc, 1, A_t, B_t, 1)`` / ``Ger(acc, 1, x_t, y_t)`` — becomes one product over
     the stacked per-step operands behind the loop.  The rewritten plan, run by the NumPy oracle, must
@@ -713,7 +713,7 @@ def test_product_accumulators_leave_the_loop_as_one_product(name):
     the runtime conditions (one-row buffer, nit-sot outputs that keep every row) are reported."""
     import interp
     from golden_util import assert_matches
-    from aesara_amd.fusion import push_out_accumulators, push_out_product_accumulators
+    from aesara_amd.scan_rewrite import push_out_accumulators, push_out_product_accumulators
     c = next(c for c in CASES if c["name"] == name)
     p1 = push_out_accumulators(case_plan(c))
     # (without the lists only buffers whose length is STATICALLY one row are rewritten: an Alloc of
@@ -787,7 +787,7 @@ def test_two_tap_gradient_scan_maps_to_two_states_on_one_buffer():
     slot of out-tap 1 (the group's own slot), tap 1 with a further slot on the same buffer for
     out-tap 2 — and tap 2 as the buffer-resident sequence."""
     from aesara_amd import scan_persist as sp
-    from aesara_amd.fusion import push_out_product_accumulators
+    from aesara_amd.scan_rewrite import push_out_product_accumulators
     c = next(c for c in CASES if c["name"] == "sm_taps_bptt_b16_f32")
     plan = push_out_product_accumulators(case_plan(c), [], [])
     node = [n for n in plan.nodes if n.op == "Scan"][1]
@@ -884,3 +884,126 @@ def test_which_golden_scans_run_as_one_launch():
                 want = expected_launch_list.get(c["name"])
                 assert want is not None and want in mode, (c["name"], mode)
     assert (persistent, all_rows, total) == (95, 6, 105), (persistent, all_rows, total)
+
+
+def test_sequence_dots_leave_the_step():
+    """scan_rewrite.hoist_sequence_dots on a hand-built step plan (sequence rows of length 3, invariant
+    matrices 2 x 3 / 3 x 2): a ``Gemv`` with constant alpha and beta == 0, a ``Gemv`` that
+    accumulates onto that product (constant beta != 0, y a hoisted row), ``Dot22(seq, inv)`` and
+    ``Dot(inv, seq)`` leave the step and enter it as further inputs; a ``Gemv`` with a run-time alpha
+    and an integer product stay where they are."""
+    from aesara_amd.scan_rewrite import hoist_sequence_dots
+    from aesara_amd.plan import Node
+    p = Plan("step", {}, [], [], [])
+    x, x2 = p.new_var("float32", [3]), p.new_var("float32", [3])                # 0, 1: sequence rows
+    xm, xi = p.new_var("float32", [None, 3]), p.new_var("int64", [3])           # 2, 3: sequence rows
+    h = p.new_var("float32", [2])                                               # 4: a state tap
+    W, W2, U = p.new_var("float32", [2, 3]), p.new_var("float32", [2, 3]), p.new_var("float32", [3, 2])   # 5, 6, 7
+    Wi, a_run = p.new_var("int64", [2, 3]), p.new_var("float32", [])            # 8, 9
+    two, half, zero, one = (p.add_const(c, "float32") for c in (2.0, 0.5, 0.0, 1.0))   # 10 .. 13
+    n2 = p.add_const(2, "int64")                                                # 14
+    y0, g1, g2, d1, d2, g3, di = (p.new_var(dt, shp) for dt, shp in (
+        ("float32", [2]), ("float32", [2]), ("float32", [2]), ("float32", [None, 2]), ("float32", [2]),
+        ("float32", [2]), ("int64", [2])))                                      # 15 .. 21
+    assert (x, x2, xm, xi, h, W, W2, U, Wi, a_run) == tuple(range(10)) and (y0, di) == (15, 21)
+    p.inputs = [x, x2, xm, xi, h, W, W2, U, Wi, a_run]
+    p.outputs = [g2, d1, d2, g3, di]
+    p.nodes = [
+        Node("AllocEmpty", [n2], [y0], {"dtype": "float32"}),
+        Node("Gemv", [y0, two, W, x, zero], [g1], {"inplace": False}),
+        Node("Gemv", [g1, half, W2, x2, one], [g2], {"inplace": False}),
+        Node("Dot22", [xm, U], [d1], {}),
+        Node("Dot", [W, x2], [d2], {}),
+        Node("Gemv", [h, a_run, W, x, one], [g3], {"inplace": False}),
+        Node("Dot", [Wi, xi], [di], {}),
+    ]
+    loop, hoists = hoist_sequence_dots(p, [0, 1, 2, 3], {5, 6, 7, 8, 9})
+    assert hoists == [
+        {"kind": "gemv", "seq": 0, "mat": 5, "alpha": 2.0, "out": 16},
+        {"kind": "gemv", "seq": 1, "mat": 6, "alpha": 0.5, "beta": 1.0, "acc": 16, "out": 17},
+        {"kind": "dot", "seq": 2, "mat": 7, "alpha": 1.0, "out": 18},
+        {"kind": "gemv", "seq": 1, "mat": 5, "alpha": 1.0, "out": 19},
+    ]
+    assert loop.name == "step_seqdots" and loop.vars is p.vars
+    assert loop.inputs == [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 18, 19]
+    assert loop.outputs == [17, 18, 19, 20, 21]
+    assert [(n.op, n.inputs, n.outputs) for n in loop.nodes] == [
+        ("AllocEmpty", [14], [15]), ("Gemv", [4, 9, 5, 0, 13], [20]), ("Dot", [8, 3], [21])]
+    assert [n for n in loop.nodes] == [p.nodes[0], p.nodes[5], p.nodes[6]]
+    # without the sequences nothing is a product over sequence rows: the plan itself comes back
+    same, none = hoist_sequence_dots(p, [], {5, 6, 7, 8, 9})
+    assert same is p and none == []
+
+
+def test_plan_queries():
+    """Plan.producers / Plan.copy / Plan.const_scalar: the producer map, the shallow copy the
+    rewrites start from, and the value of a size-1 constant — a constant of two elements and one
+    held as an array (more than 4096 elements: ``"array"``, not ``"data"``) read as None, as does a
+    variable that is no constant."""
+    from aesara_amd.plan import Node
+    p = Plan("q", {}, [], [], [])
+    x = p.new_var("float32", [None])
+    c1, ci, c2 = p.add_const(2.5, "float32"), p.add_const([[7]], "int64"), p.add_const([1.0, 2.0], "float64")
+    big = p.add_const(np.zeros(5000), "float64")
+    one_big = p.new_var("float64", [1], None, {"shape": [1], "array": np.ones(1)})
+    y, z, w = p.new_var("float32", [None]), p.new_var("float32", [None]), p.new_var("float32", [None])
+    n0, n1 = Node("Elemwise", [x, c1], [y], {}), Node("Split", [y], [z, w], {})
+    p.inputs, p.outputs, p.nodes = [x], [z, w], [n0, n1]
+    assert "array" in p.vars[big].const and "data" not in p.vars[big].const
+    assert [p.const_scalar(v) for v in (x, c1, ci, c2, big, one_big, y)] == [None, 2.5, 7, None, None, None, None]
+    assert type(p.const_scalar(c1)) is float and type(p.const_scalar(ci)) is int
+    prod = p.producers()
+    assert prod == {y: n0, z: n1, w: n1} and prod[y] is n0 and prod[w] is n1
+    q = p.copy()
+    assert (q.name, q.vars, q.inputs, q.outputs, q.nodes) == (p.name, p.vars, p.inputs, p.outputs, p.nodes)
+    assert all(a is not b for a, b in ((q.vars, p.vars), (q.inputs, p.inputs), (q.outputs, p.outputs), (q.nodes, p.nodes)))
+    assert q.vars[x] is p.vars[x] and q.nodes[0] is n0              # shallow: Var / Node objects are shared
+    v = q.new_var("int64", [])
+    assert v not in p.vars and v == w + 1
+    r = p.copy("other", nodes=[n1])
+    assert r.name == "other" and r.nodes == [n1] and p.nodes == [n0, n1] and p.name == "q"
+
+
+def test_scan_slot_layout():
+    """scan_rewrite.ScanSlots on a hand-built Scan node with 2 sequences, one mit-mot (3 input taps,
+    2 output taps), one mit-sot (2 taps), 3 sit-sots, 1 shared, 2 nit-sots and 2 non-sequences.  The
+    positions are counted by hand in the reference's order (scan/op.py ``ScanMethodsMixin``):
+
+    * node.inputs   (13): n_steps | s s | mm | ms | ss ss ss | sh | len len | non non
+    * node.outputs   (8): mm | ms | ss ss ss | nit nit | sh
+    * inner.inputs  (13): s s | mm mm mm | ms ms | ss ss ss | sh | non non
+    * inner.outputs  (9): mm mm | ms | ss ss ss | nit nit | sh"""
+    from aesara_amd.plan import Node
+    from aesara_amd.scan_rewrite import ScanSlots
+    inner = Plan("step", {}, list(range(100, 113)), list(range(200, 209)), [])
+    node = Node("Scan", list(range(300, 313)), list(range(400, 408)), {
+        "inner": inner, "n_seqs": 2, "mit_mot_in_slices": [[0, 2, 1]], "mit_mot_out_slices": [[2, 1]],
+        "mit_sot_in_slices": [[-2, -1]], "sit_sot_in_slices": [[-1], [-1], [-1]], "n_shared_outs": 1,
+        "n_nit_sot": 2, "n_non_seqs": 2})
+    L = ScanSlots(node)
+    assert (L.n_seqs, L.n_mm, L.n_ms, L.n_ss, L.n_sh, L.n_nit, L.n_non) == (2, 1, 1, 3, 1, 2, 2)
+    assert [L.in_seq(k) for k in range(2)] == [1, 2]
+    assert [L.in_init(q) for q in range(3)] == [5, 6, 7]
+    assert [L.in_nit_len(j) for j in range(2)] == [9, 10] and L.in_non0 == 11
+    assert [L.out_ss(q) for q in range(3)] == [2, 3, 4] and [L.out_nit(j) for j in range(2)] == [5, 6]
+    assert [L.iin_tap(q) for q in range(3)] == [7, 8, 9] and L.iin_inv0 == 11
+    assert [L.iout_ss(q) for q in range(3)] == [3, 4, 5] and [L.iout_nit(j) for j in range(2)] == [6, 7]
+    dropped = L.drop_sit_sots({0, 2})
+    assert dropped == [
+        [300, 301, 302, 303, 304, 306, 308, 309, 310, 311, 312],
+        [400, 401, 403, 405, 406, 407],
+        [100, 101, 102, 103, 104, 105, 106, 108, 110, 111, 112],
+        [200, 201, 202, 204, 206, 207, 208]]
+    assert L.insert_nit_sots(dropped, None, [300, 300], [500, 501], [600, 601], n_dropped=2) == [
+        [300, 301, 302, 303, 304, 306, 308, 309, 310, 300, 300, 311, 312],
+        [400, 401, 403, 405, 406, 500, 501, 407],
+        [100, 101, 102, 103, 104, 105, 106, 108, 110, 111, 112],
+        [200, 201, 202, 204, 206, 207, 600, 601, 208]]
+    # nit-sot 0 replaced by two blocks (what split_assembled_columns does), nothing dropped
+    whole = [list(node.inputs), list(node.outputs), list(inner.inputs), list(inner.outputs)]
+    assert L.insert_nit_sots(whole, 0, [309, 309], [500, 501], [600, 601], n_old=1) == [
+        [300, 301, 302, 303, 304, 305, 306, 307, 308, 309, 309, 310, 311, 312],
+        [400, 401, 402, 403, 404, 500, 501, 406, 407],
+        list(range(100, 113)),
+        [200, 201, 202, 203, 204, 205, 600, 601, 207, 208]]
+    assert node.inputs == list(range(300, 313)) and inner.outputs == list(range(200, 209))   # (nothing in place)

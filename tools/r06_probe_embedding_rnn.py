@@ -1,7 +1,7 @@
 """Round 6 probe: an RNN whose step looks its input up itself (golden plan scan_embedding_lookup_batch_f32:
 h_t = tanh(E[idx_t] + h_{t-1} U), cost = sum(h_T^2), outputs hs, dcost/dU, dcost/dE) at T = 512, B = 64,
 H = 1024, a 50 000-row table.  default: lookup + table-gradient scatter taken out of the loops
-(fusion.push_out_sequence_glue / push_out_product_accumulators), both Scans on the persistent matrix kernel;
+(scan_rewrite.push_out_sequence_glue / push_out_product_accumulators), both Scans on the persistent matrix kernel;
 launch list: the same plan with AESARA_HIP_SCAN_PERSIST=0; unfused: fuse=False (the graph as lowered: lookup and
 scatter inside the step loops, one host read of the indices per step)."""
 import json, os, sys, time

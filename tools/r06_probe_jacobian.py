@@ -1,5 +1,5 @@
 """Round 6 probe: gradient.jacobian's row loop (golden plan scan_map_jacobian_rows: y = tanh(W x) * sum(x),
-J = dy/dx) as ONE evaluation over whole sequences (fusion.batch_map_step) vs the step loop on the launch
+J = dy/dx) as ONE evaluation over whole sequences (scan_rewrite.batch_map_step) vs the step loop on the launch
 list / hipGraph, and aesara.map over matrix rows (scan_map_rows_reduce_broadcast).  usage: tools/r06_probe_jacobian.py"""
 import json, os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -23,7 +23,7 @@ tot = collections.Counter()
 for c in per_file.values():
     tot.update(c)
 print("# Scans of the reference's OWN test files under mode HIP: persistent one-launch kernel / one evaluation over")
-print("# whole sequences (no recurrence: fusion.batch_map_step) / launch list")
+print("# whole sequences (no recurrence: scan_rewrite.batch_map_step) / launch list")
 print("# (tests/hip_suite_plugin.py, executor = prebuild: the PlanExecutor's dry run records PlanExecutor.scan_modes;")
 print("#  AESARA_HIP_SUITE_SCANLOG=... python tests/reference_files.py --executor prebuild; tools/scan_mode_summary.py;")
 print("#  one entry per DISTINCT compiled function of a test)")
