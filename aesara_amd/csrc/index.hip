@@ -744,9 +744,17 @@ __global__ __launch_bounds__(256) void linearize_kernel(LinArgs a) {
     bool ok = true;
     for (int d = 0; d < a.nidx; ++d) {
       const int64_t v = load_index(a.idx[d], a.dtype[d], j * a.stride[d]);
+      if (a.dtype[d] == AHIP_U64 && v < 0) {
+        // a uint64 index beyond int64 must not wrap into a valid negative one: the code resolve() gives
+        atomicCAS(reinterpret_cast<unsigned long long*>(a.bad), 0ULL, 0x7FFFFFFFFFFFFFFFULL);
+        ok = false;
+        continue;
+      }
       const int64_t w = v < 0 ? v + a.dim[d] : v;
       if (w < 0 || w >= a.dim[d]) {
-        unsigned long long code = (unsigned long long)(v >= 0 ? v + 1 : v);
+        unsigned long long code =
+            v >= 0 ? (unsigned long long)(v < 0x7FFFFFFFFFFFFFFELL ? v : 0x7FFFFFFFFFFFFFFELL) + 1ULL
+                   : (unsigned long long)v;
         atomicCAS(reinterpret_cast<unsigned long long*>(a.bad), 0ULL, code);
         ok = false;
       } else {

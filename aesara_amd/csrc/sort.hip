@@ -30,11 +30,18 @@ struct SortArgs {
 };
 AHIP_PTRS_BEGIN(SortArgs) AHIP_PTR1(x) AHIP_PTR1(keys_out) AHIP_PTR1(idx_out) AHIP_PTRS_END
 
+// LDS layout: n2 keys, then n2 int positions.  1 or 2 keys of 1 byte (1 key of 2 bytes) end off a
+// 4-byte boundary, so the positions start at the next one (no change for n2 >= 4).
+template <typename T>
+__host__ __device__ __forceinline__ size_t pos_offset(int n2) {
+  return ((size_t)n2 * sizeof(T) + 3) & ~size_t(3);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void sort_rows_kernel(SortArgs a) {
-  extern __shared__ unsigned char smem[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* key = reinterpret_cast<T*>(smem);
-  int* pos = reinterpret_cast<int*>(smem + (size_t)a.n2 * sizeof(T));
+  int* pos = reinterpret_cast<int*>(smem + pos_offset<T>(a.n2));
   const T* __restrict__ x = static_cast<const T*>(a.x);
   for (int64_t r = blockIdx.x; r < a.rows; r += gridDim.x) {
     const T* row = x + r * a.x_rs;
@@ -73,7 +80,7 @@ int run_sort(SortArgs& a, hipStream_t s) {
   int n2 = 1;
   while (n2 < a.n) n2 <<= 1;
   a.n2 = n2;
-  const size_t shmem = (size_t)n2 * (sizeof(T) + sizeof(int));
+  const size_t shmem = pos_offset<T>(n2) + (size_t)n2 * sizeof(int);
   AHIP_REQUIRE(shmem <= 64 * 1024, "sort: rows of %lld elements do not fit in LDS", (long long)a.n);
   int64_t want = a.rows, cap = (int64_t)ahip_cu_count() * 8;
   if (want > cap) want = cap;
@@ -100,7 +107,7 @@ AHIP_PTRS_BEGIN(ChunkArgs) AHIP_PTR1(x) AHIP_PTR1(keys) AHIP_PTR1(idx) AHIP_PTRS
 
 template <typename T>
 __global__ __launch_bounds__(256) void sort_chunks_kernel(ChunkArgs a) {
-  extern __shared__ unsigned char smem[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* key = reinterpret_cast<T*>(smem);
   int* pos = reinterpret_cast<int*>(smem + (size_t)a.C * sizeof(T));
   const T* __restrict__ x = static_cast<const T*>(a.x);
