@@ -200,6 +200,14 @@ SIGNATURES = {
     "ahip_geqr2_panel": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_larft": (i32, [i32, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_qr_extract_r": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, i64, vp]),
+    "ahip_csr_narrow_max": (i32, []),
+    "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),
+    "ahip_csr_to_dense": (i32, [i32, i64, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp]),
+    "ahip_csr_mul_dense": (i32, [i32, i64, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp]),
+    "ahip_dense_count_rows": (i32, [i32, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_dense_fill_csr": (i32, [i32, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "ahip_csr_flip_finish": (i32, [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
     "ahip_linearize_indices": (i32, [i32, p_vp, C.POINTER(C.c_int), p_i64, p_i64, p_i64, i64, vp,
                                      vp, vp]),
     "ahip_searchsorted": (i32, [i32, vp, i64, i64, vp, i64, i32, vp, vp, vp]),

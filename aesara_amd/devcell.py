@@ -106,7 +106,7 @@ class DeviceFilterType:
     in-place Op would destroy; this linker's rewrite query excludes ``inplace`` and the executor
     only ever writes into buffers it allocated itself, so there is nothing for it to protect.
     """
-    __slots__ = ("_t", "_want", "_ndim", "_static", "_np")
+    __slots__ = ("_t", "_want", "_ndim", "_static", "_np", "_sparse")
 
     def __init__(self, t):
         t = t._t if isinstance(t, DeviceFilterType) else t
@@ -124,8 +124,17 @@ class DeviceFilterType:
                 or np.dtype(npdt.name) is not npdt:
             npdt = None
         object.__setattr__(self, "_np", npdt)
+        # the format of a ``SparseTensorType`` (None: a dense type): such a cell also takes a
+        # ``sparse.DeviceSparse`` of that format and data dtype as it is
+        fmt = getattr(t, "format", None)
+        object.__setattr__(self, "_sparse", fmt if type(t).__name__.startswith("Sparse") else None)
 
     def filter(self, value, strict=False, allow_downcast=None):
+        if self._sparse is not None:
+            from .sparse import DeviceSparse, check_argument
+            if isinstance(value, DeviceSparse):
+                return check_argument(value, self._sparse, str(self._t.dtype))
+            return self._t.filter(value, strict=strict, allow_downcast=allow_downcast)
         if type(value) is np.ndarray:
             # (the 0-d ``mu`` / ``sigma`` / learning-rate arguments of every call: 0.3 us instead of
             # the 1.9 us of the general filter below, which reaches the same ``return data``)

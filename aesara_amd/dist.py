@@ -77,7 +77,10 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   # (every rank must draw the same numbers from the same state: replicated)
                   "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform",
                   # (a factorisation couples every row and column of its matrix: not batch-splittable)
-                  "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det", "QR"}
+                  "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det", "QR",
+                  # (the members of a sparse value address each other: splitting `data` alone means nothing)
+                  "StructuredDot", "SparseDot", "SampledDot", "DenseFromSparse", "SparseFromDense", "SpSum",
+                  "MulSD"}
 
 
 def _const_scalar(plan: Plan, vid: int):

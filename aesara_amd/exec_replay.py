@@ -9,6 +9,7 @@ from __future__ import annotations
 from .exec_common import *  # noqa: F401,F403
 from .exec_common import (_I64, _VP, _i64arr, _Kernels, _FakeBuf, _CAST_SCALARS, _prod, _Arena, _os, _time)  # noqa: F401
 from .exec_linalg import is_linalg_code, linalg_error
+from .exec_sparse import is_sparse_code, sparse_error
 
 
 class ReplayMixin:
@@ -597,6 +598,13 @@ class ReplayMixin:
             # the info word of a dense solve (exec_linalg.py): singular matrix / non-finite operand
             st = self.steps[si] if si < len(self.steps) else None
             e = linalg_error(code, st.node.op if st is not None and st.kind == "node" else None)
+            if note:
+                e.args = (e.args[0] + note,)
+        elif is_sparse_code(code):
+            # the info word of a sparse kernel (exec_sparse.py): a malformed operand, named by the node
+            node = self.steps[si].node if si < len(self.steps) and self.steps[si].kind == "node" else None
+            e = sparse_error(code, node.op if node is not None else None,
+                             node.params.get("name") if node is not None else None)
             if note:
                 e.args = (e.args[0] + note,)
         else:

@@ -135,18 +135,43 @@ class HipLinker(JITLinker):
         # (types.py:1060-1069), never to the caller: they stay device tensors
         self._update_outputs = {fgraph.outputs[i]
                                 for i in getattr(fgraph, "update_mapping", None) or {}}
+        self._update_positions = set(getattr(fgraph, "update_mapping", None) or {})
         return self.plan
 
     def jit_compile(self, plan):
         if self.executor_factory is not None:
-            return self._with_writeback(self.executor_factory(plan))
+            return self._with_writeback(self._with_sparse(self.executor_factory(plan), plan))
         from .executor import PlanExecutor  # imports the C-ABI; fails loudly if missing
 
         ex = PlanExecutor(plan, use_graph=self.use_graph, check_indices=self.check_indices)
         if self.profile:
             ex.enable_profile()
         self.executor = ex
-        return self._with_writeback(ex)
+        return self._with_writeback(self._with_sparse(ex, plan))
+
+    def _with_sparse(self, ex, plan):
+        """Sparse values cross the boundary as their members (``Plan.sparse``, aesara_amd/sparse.py): a
+        SciPy matrix or ``DeviceSparse`` argument is taken apart in front of the executor call, sparse
+        results are put together behind it — a ``DeviceSparse`` by default, a SciPy matrix of the
+        declared format with ``return_numpy`` and for an ``updates=`` result (the cell of a sparse
+        shared variable holds a SciPy matrix)."""
+        spec = getattr(plan, "sparse", None)
+        if not spec:
+            return ex
+        from .sparse import collect_results, expand_args
+        sp_in, sp_out = spec["inputs"], spec["outputs"]
+        n = self._n_outputs
+        to_host = {k for k, _f, _p in sp_out if self.return_numpy or k in self._update_positions}
+
+        def call(*args):
+            res = ex(*expand_args(args, sp_in)) if sp_in else ex(*args)
+            if res is None or not sp_out:       # (None: the stand-in executors of lowering tests)
+                return res
+            res = collect_results(res, sp_out, n)
+            for k in to_host:
+                res[k] = res[k].to_scipy()
+            return res
+        return call
 
     def _with_writeback(self, ex):
         wb = [i for i, _v in getattr(self, "_writeback", ())]

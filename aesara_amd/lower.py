@@ -148,6 +148,9 @@ class _Ctx:
         self.plan = plan
         self.vmap = {}
         self.slices = {}     # SliceType variable -> [start, stop, step] variables (MakeSlice)
+        self.sparse = {}     # sparse variable -> lower_sparse.SparseRec (its members as plan variables)
+        self.lazy = {}       # variable -> function emitting its node at the first use (csm_shape)
+        self.sparse_shape = {}   # csm_shape result -> (rows, cols) plan variables of its matrix
         self.inner_rewriter = inner_rewriter
 
     def vid(self, v):
@@ -155,9 +158,15 @@ class _Ctx:
 
         if v in self.vmap:
             return self.vmap[v]
+        if v in self.lazy:
+            self.vmap[v] = self.lazy.pop(v)()
+            return self.vmap[v]
+        if v in self.sparse or (hasattr(v.type, "format") and type(v.type).__name__.startswith("Sparse")):
+            # a sparse value is a record of plan variables (lower_sparse.py), never ONE variable: only
+            # the handlers of sparse Ops (and the graph boundary) take it apart
+            raise UnsupportedOp(f"non-tensor variable type Sparse ({v.type}): used where a dense "
+                                "tensor is expected")
         if isinstance(v, Constant):
-            if hasattr(v.type, "format") and type(v.type).__name__.startswith("Sparse"):
-                raise UnsupportedOp(f"non-tensor variable type Sparse ({v.type})")
             data = np.asarray(v.data)
             vid = self.plan.add_const(data, dtype=v.type.dtype, name=None)
             # keep static broadcast pattern of the constant's type
@@ -210,8 +219,14 @@ def lower_fgraph(fgraph, order=None, name="fgraph", inner_rewriter=None, extra_o
     _register_handlers()
     plan = Plan(name, {}, [], [], [])
     ctx = _Ctx(plan, inner_rewriter)
-    for v in fgraph.inputs:
-        plan.inputs.append(ctx.new(v))
+    from . import lower_sparse
+    sp_in, sp_out = [], []
+    for k, v in enumerate(fgraph.inputs):
+        if lower_sparse.is_sparse(v):
+            sp_in.append([k, lower_sparse.new_input(ctx, v, k, UnsupportedOp).format, len(plan.inputs)])
+            plan.inputs.extend(ctx.sparse[v].members())
+        else:
+            plan.inputs.append(ctx.new(v))
     # plan variable -> position (in ``order``) of the Apply node it was lowered from: how the
     # linker maps a failing / timed executor step back to the graph (raise_with_op, fn.profile).
     # A plain attribute, not part of the serialised plan.
@@ -227,7 +242,16 @@ def lower_fgraph(fgraph, order=None, name="fgraph", inner_rewriter=None, extra_o
                 origin.setdefault(ctx.vmap[o], k)
     # ``extra_outputs``: variables the linker needs next to the graph's outputs (the final content
     # of an input buffer a destructive Op overwrites: linker.HipLinker write-back)
-    plan.outputs = [ctx.vid(o) for o in fgraph.outputs] + [ctx.vid(o) for o in extra_outputs]
+    for k, o in enumerate(fgraph.outputs):
+        if lower_sparse.is_sparse(o):
+            rec = lower_sparse.record(ctx, o, UnsupportedOp)
+            sp_out.append([k, rec.format, len(plan.outputs)])
+            plan.outputs.extend(rec.members())
+        else:
+            plan.outputs.append(ctx.vid(o))
+    plan.outputs += [ctx.vid(o) for o in extra_outputs]
+    if sp_in or sp_out:
+        plan.sparse = {"inputs": sp_in, "outputs": sp_out}
     plan.var_origin = origin
     return plan
 
@@ -884,6 +908,8 @@ def _register_handlers():
     lower_rng.register(hip_lower, _static_shape, UnsupportedOp)
     from . import lower_linalg
     lower_linalg.register(hip_lower, _static_shape, UnsupportedOp)
+    from . import lower_sparse
+    lower_sparse.register(hip_lower, _static_shape, UnsupportedOp)
 
     @hip_lower.register(Scan)
     def _(op, node, ctx):

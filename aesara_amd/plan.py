@@ -126,6 +126,11 @@ class Plan:
     inputs: List[int]
     outputs: List[int]
     nodes: List[Node]
+    # sparse values at the boundary (None: there is none).  {"inputs": [[graph position, format,
+    # first plan position], ...], "outputs": [...]}: the value at that position of the graph's
+    # input / output list is the five plan inputs / outputs from ``first plan position`` on — data,
+    # indices, indptr, rows, cols (lower_sparse.py; put together again by aesara_amd/sparse.py)
+    sparse: Optional[Dict[str, Any]] = None
 
     # ---- construction helpers -------------------------------------------------
     def new_var(self, dtype, shape, name=None, const=None) -> int:
@@ -145,7 +150,7 @@ class Plan:
 
     # ---- (de)serialisation ----------------------------------------------------
     def to_json(self):
-        return {
+        d = {
             "version": PLAN_VERSION,
             "name": self.name,
             "vars": [v.to_json() for v in self.vars.values()],
@@ -153,6 +158,9 @@ class Plan:
             "outputs": self.outputs,
             "nodes": [n.to_json() for n in self.nodes],
         }
+        if self.sparse:         # (absent without sparse values: such plans serialise as they always did)
+            d["sparse"] = self.sparse
+        return d
 
     @staticmethod
     def from_json(d):
@@ -160,7 +168,7 @@ class Plan:
             raise ValueError(f"unsupported plan version {d.get('version')}")
         vs = {v["id"]: Var.from_json(v) for v in d["vars"]}
         return Plan(d["name"], vs, list(d["inputs"]), list(d["outputs"]),
-                    [Node.from_json(n) for n in d["nodes"]])
+                    [Node.from_json(n) for n in d["nodes"]], d.get("sparse"))
 
     def dumps(self, **kw):
         return json.dumps(self.to_json(), **kw)
@@ -172,7 +180,7 @@ class Plan:
     def copy(self, name=None, nodes=None):
         """Shallow copy: own var table and lists (``nodes`` instead of this plan's), shared Var / Node objects."""
         return Plan(name or self.name, dict(self.vars), list(self.inputs), list(self.outputs),
-                    list(self.nodes if nodes is None else nodes))
+                    list(self.nodes if nodes is None else nodes), self.sparse)
 
     # ---- queries ----------------------------------------------------------------
     def producers(self):

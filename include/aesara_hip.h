@@ -619,6 +619,53 @@ int ahip_larft(int dtype, int64_t nb, const void* G, int64_t g_rs, int64_t g_cs,
                int64_t t_rs, int64_t t_cs, void* stream);
 int ahip_qr_extract_r(int dtype, int64_t rows, int64_t cols, const void* A, int64_t a_rs, int64_t a_cs,
                       void* R, int64_t r_rs, int64_t r_cs, void* stream);
+/* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
+ * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
+ * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
+ * indices[nnz], indptr[M + 1]) with `minor` the extent the indices address; a CSC value is passed as
+ * the CSR view of its transpose (the caller swaps extents and strides).  Dense operands take (row,
+ * col) element strides.  Every extent and nnz stay below 2^31.  No float atomics: every sum has a
+ * fixed order.
+ * info: optional device word (uint64, zero = no error), shared with K18's words.  An index outside
+ * [0, minor) or a row range that is not 0 <= start <= end <= nnz is recorded with one atomic max of
+ * AHIP_LINALG_INFO_TAG | AHIP_SPARSE_MALFORMED << 32 | AHIP_SPARSE_BAD_*, and the entry / row is
+ * skipped: nothing is read or written through it.
+ *   csr_spmm:        out[r, c] = sum over row r's entries k, in stored order per lane, of
+ *                    data[perm ? perm[k] : k] * B[indices[k], c].  ncols <= ahip_csr_narrow_max():
+ *                    lanes across the entries and a fixed fold; wider: lanes across the columns
+ *                    (16-byte loads when b_cs == 1 and B's rows are 16-byte aligned).
+ *   csr_sddmm:       out[k] = sum_c G[row(k), c] * B[indices[k], c] for every stored entry.
+ *   csr_to_dense:    D (zero-filled by the caller) += the entries, each row in stored order.
+ *   csr_mul_dense:   out[k] = data[k] * D[row(k), indices[k]].
+ *   dense_count_rows / dense_fill_csr: counts[r] = number of entries of row r of D with value != 0
+ *                    (-0.0 dropped, NaN kept); then, with indptr the exclusive running sum of the
+ *                    counts, those entries and their columns in ascending column order.
+ *   csr_flip_finish: the other orientation of a pattern from the stable ascending argsort of its
+ *                    indices (keys[p] = indices[perm[p]], K13): new_indices[p] = the row of entry
+ *                    perm[p], new_indptr[j] (minor + 1 entries) = the first p with keys[p] >= j.  The
+ *                    flipped value is csr_spmm's (perm, new_indices, new_indptr) with extents swapped;
+ *                    it is in range by construction.  Needs indptr[0] == 0 and indptr[M] == nnz. */
+#define AHIP_SPARSE_MALFORMED 1
+#define AHIP_SPARSE_BAD_INDEX 1
+#define AHIP_SPARSE_BAD_INDPTR 2
+int ahip_csr_narrow_max(void);
+int ahip_csr_spmm(int dtype, int64_t M, int64_t minor, int64_t ncols, int64_t nnz, const void* data,
+                  const int64_t* perm, const int* indices, const int* indptr, const void* B, int64_t b_rs,
+                  int64_t b_cs, void* out, int64_t o_rs, int64_t o_cs, void* info, void* stream);
+int ahip_csr_sddmm(int dtype, int64_t M, int64_t minor, int64_t ncols, int64_t nnz, const int* indices,
+                   const int* indptr, const void* G, int64_t g_rs, int64_t g_cs, const void* B, int64_t b_rs,
+                   int64_t b_cs, void* out, void* info, void* stream);
+int ahip_csr_to_dense(int dtype, int64_t M, int64_t minor, int64_t nnz, const void* data, const int* indices,
+                      const int* indptr, void* D, int64_t d_rs, int64_t d_cs, void* info, void* stream);
+int ahip_csr_mul_dense(int dtype, int64_t M, int64_t minor, int64_t nnz, const void* data, const int* indices,
+                       const int* indptr, const void* D, int64_t d_rs, int64_t d_cs, void* out, void* info,
+                       void* stream);
+int ahip_dense_count_rows(int dtype, int64_t M, int64_t minor, const void* D, int64_t d_rs, int64_t d_cs,
+                          int* counts, void* stream);
+int ahip_dense_fill_csr(int dtype, int64_t M, int64_t minor, int64_t nnz, const void* D, int64_t d_rs,
+                        int64_t d_cs, const int* indptr, void* data, int* indices, void* stream);
+int ahip_csr_flip_finish(int64_t M, int64_t minor, int64_t nnz, const int* keys, const int64_t* perm,
+                         const int* indptr, int* new_indices, int* new_indptr, void* info, void* stream);
 /* Row argmax, replaces tensor/math.py:330 Argmax (perform :388: np.argmax over the reduced axes
  * moved last and flattened).  x is viewed as [nrows, k] with element strides x_rs / x_cs; out[r]
  * = index of the first maximum of row r; a NaN counts as the maximum (first NaN wins).  When
