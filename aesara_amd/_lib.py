@@ -200,6 +200,15 @@ SIGNATURES = {
     "ahip_geqr2_panel": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_larft": (i32, [i32, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_qr_extract_r": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, i64, vp]),
+    "ahip_syev_tile": (i32, [i32, i32, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64,
+                             vp, i64, C.c_double, vp, vp, vp]),
+    "ahip_syev_gather": (i32, [i32, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_syev_apply": (i32, [i32, i64, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
+    "ahip_syev_off": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
+    "ahip_potrf_diag": (i32, [i32, i32, i64, vp, i64, i64, i64, vp, vp]),
+    "ahip_syev_diag": (i32, [i32, i64, vp, i64, i64, vp, vp]),
+    "ahip_scale_cols": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp]),
+    "ahip_sym_fold": (i32, [i32, i32, i64, vp, i64, i64, vp, i64, i64, vp]),
     "ahip_csr_narrow_max": (i32, []),
     "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),

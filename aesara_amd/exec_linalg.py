@@ -38,6 +38,7 @@ from .exec_common import (_I64, _VP, _i64arr, _Kernels, _FakeBuf, _CAST_SCALARS,
 NB = 64                       # AHIP_LINALG_NB: rows of a diagonal block / columns of a panel
 INFO_TAG = 1 << 62            # AHIP_LINALG_INFO_TAG
 SINGULAR, NONFINITE = 2, 3    # AHIP_LINALG_SINGULAR / _NONFINITE
+EIG = 0                       # AHIP_LINALG_EIG (kind 1 is the sparse kernels', exec_sparse.py)
 LINALG_OPS = ("SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det")
 QR_MODES = ("reduced", "complete", "r", "raw")
 
@@ -45,8 +46,9 @@ QR_MODES = ("reduced", "complete", "r", "raw")
 def is_linalg_code(code):
     """Whether an error word holds an info code of these kernels and not a bad index of the index
     kernels, which share the step's word (index + 1, saturated at 2^63 - 1 for a uint64 index beyond
-    int64): the tag bit alone above a kind of two bits — every other bit from 34 up is zero."""
-    return code > 0 and (code >> 34) == (INFO_TAG >> 34) and ((code >> 32) & 3) in (SINGULAR, NONFINITE)
+    int64): the tag bit alone above a kind of two bits — every other bit from 34 up is zero.  Kind 1
+    belongs to the sparse kernels (exec_sparse.py)."""
+    return code > 0 and (code >> 34) == (INFO_TAG >> 34) and ((code >> 32) & 3) in (EIG, SINGULAR, NONFINITE)
 
 
 def linalg_error(code, opname=None):
@@ -56,6 +58,13 @@ def linalg_error(code, opname=None):
     kind, k = (code >> 32) & 0xFF, 0xFFFFFFFF - (code & 0xFFFFFFFF)
     if kind == NONFINITE:
         return ValueError("array must not contain infs or NaNs")
+    if kind == EIG:
+        # (exec_eig.py) k = 0: the Jacobi sweeps ran out; k >= 1: scipy.linalg.eigh's report of potrf
+        if k == 0:
+            return np.linalg.LinAlgError("Eigenvalues did not converge")
+        return np.linalg.LinAlgError(f"The leading minor of order {k} of B is not positive definite. The "
+                                     "factorization of B could not be completed and no eigenvalues or "
+                                     "eigenvectors were computed.")
     if opname == "SolveTriangular":
         # (trtrs reports the 1-based index; SciPy prints info - 1)
         return np.linalg.LinAlgError(f"singular matrix: resolution failed at diagonal {k}")

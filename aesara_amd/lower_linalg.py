@@ -11,9 +11,14 @@ nlinalg.py:129, ``Det.grad`` :219), so nothing else is needed for ``aesara.grad`
 (``Q, R`` for 'reduced' / 'complete', ``h, tau`` for 'raw') or one ('r').  The Op has no ``grad``, so
 neither has the lowering (csrc/qr.hip; executor: exec_linalg.py).
 
+``Eigvalsh`` and ``EigvalshGrad`` (``slinalg.eigvalsh`` and its ``grad``, slinalg.py:446 / :493) lower
+to plan ops of the same names with their ``lower``: one operand for the standard problem (``b`` given as
+``NoneConst``), two for the generalised one, three for the gradient (csrc/eig.hip; executor:
+exec_eig.py).
+
 ``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``MatrixPinv``, ``Lstsq``,
-``Eigvalsh``, ``Expm``, the Lyapunov solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they
-are refused by name like every Op without one.
+``Expm``, the Lyapunov solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they are refused by
+name like every Op without one.
 
 Registered by ``lower._register_handlers`` like lower_pool.py; every handler cites the reference Op
 it restates.
@@ -34,7 +39,7 @@ def family(name):
 
 def register(hip_lower, static_shape, UnsupportedOp):                       # noqa: N803
     from aesara.tensor.nlinalg import Det, MatrixInverse, QRFull
-    from aesara.tensor.slinalg import CholeskySolve, Solve, SolveTriangular
+    from aesara.tensor.slinalg import CholeskySolve, Eigvalsh, EigvalshGrad, Solve, SolveTriangular
 
     from .lower_more import _B
 
@@ -97,3 +102,15 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
             raise UnsupportedOp(f"{family('QRFull')} for mode = {op.mode!r} (one of "
                                 f"{', '.join(QR_MODES)})")
         _emit("QR", node, ctx, {"mode": str(op.mode)})
+
+    @hip_lower.register(Eigvalsh)
+    def _(op, node, ctx):
+        # reference: slinalg.py:446 Eigvalsh (perform :476 scipy.linalg.eigvalsh(a, b, lower); make_node
+        # :458 takes one input when b is NoneConst, else two and upcasts them)
+        _emit("Eigvalsh", node, ctx, {"lower": bool(op.lower)})
+
+    @hip_lower.register(EigvalshGrad)
+    def _(op, node, ctx):
+        # reference: slinalg.py:493 EigvalshGrad (perform :533 scipy.linalg.eigh(a, b, lower), then
+        # v diag(gw) v^T and -v diag(gw w) v^T folded into the named triangle)
+        _emit("EigvalshGrad", node, ctx, {"lower": bool(op.lower)})

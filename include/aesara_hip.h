@@ -619,6 +619,58 @@ int ahip_larft(int dtype, int64_t nb, const void* G, int64_t g_rs, int64_t g_cs,
                int64_t t_rs, int64_t t_cs, void* stream);
 int ahip_qr_extract_r(int dtype, int64_t rows, int64_t cols, const void* A, int64_t a_rs, int64_t a_cs,
                       void* R, int64_t r_rs, int64_t r_cs, void* stream);
+/* ---- K21: symmetric eigenvalues (two-sided Jacobi) and the Cholesky step of the generalised problem
+ * the kernels under tensor/slinalg.py:446 Eigvalsh / :493 EigvalshGrad (scipy.linalg.eigvalsh / eigh).
+ * dtype: AHIP_F32 or AHIP_F64; (row, col) element strides; extents below 2^30.  The caller owns the
+ * tournament and sweep loops; every dependency between workgroups is a launch boundary and every
+ * fold has a fixed order.  Rotations are ordered round-robin: for m2 players (even), step k of
+ * m2 - 1 pairs (m2 - 1, k) and ((k + i) mod (m2 - 1), (k - i) mod (m2 - 1)), i = 1 .. m2 / 2 - 1.
+ * status: device record of AHIP_SYEV_STATUS_WORDS uint64 words, zeroed by the caller: [0] done,
+ * [1] the largest sweep count of any tile so far, [2] / [3] the bits of the doubles off_F^2 and
+ * ||A||_F^2 of the last syev_off, then its workgroup partials.
+ * info: the node's info word of K18; kind AHIP_LINALG_EIG with k = 0 (no convergence after
+ * AHIP_SYEV_NSWEEP sweeps) or k >= 1 (the leading minor of order k of B is not positive definite).
+ *   syev_tile:   a batch of symmetric m x m tiles (m <= AHIP_SYEV_TILE), ONE workgroup a tile, the tile
+ *                and the accumulated rotations J resident in LDS.  Reads only the triangle `lower`
+ *                names.  Sweeps until off_F^2 <= eps^2 tol_scale ||A||_F^2 (norms in double; a NaN or
+ *                an info word that is already set ends the sweeps).  Writes, where the pointer is
+ *                not null: S the rotated tile, J (columns = eigenvectors), w the diagonal of S.
+ *   syev_gather: T[t] (contiguous 64 x 64) = the four 32 x 32 blocks (p, q) x (p, q), p < q, of pair
+ *                t of `step` in a tournament of nb blocks (nb even; A is 32 nb square).
+ *   syev_apply:  Y[:, p|q] = X[:, p|q] J[t] for every pair of `step`, out of place, on the
+ *                16x16x4 matrix instructions; X, Y: rows x 32 nb; J: nb / 2 contiguous 64 x 64.
+ *   syev_off:    status[2], [3] = off_F^2, ||A||_F^2 of the LOWER triangle of A, mirrored; status[0]
+ *                = off_F^2 <= eps^2 ||A||_F^2, or not comparable, or *info != 0.
+ *   potrf_diag:  Cholesky of ONE nb x nb diagonal block (nb <= AHIP_LINALG_NB) in place in the named
+ *                triangle, by one workgroup; a pivot that is not positive and finite records
+ *                k = base + its index + 1 and leaves the block as it was.
+ *   syev_diag:   w[i] = A[i, i].
+ *   scale_cols:  out[:, j] = V[:, perm[j]] * g[j] * h[j] (perm, g, h optional).
+ *   sym_fold:    out = tri0(G) + tri1(G)^T of EigvalshGrad.perform: g_ij + g_ji in the named triangle
+ *                below / above the diagonal, g_ii on it, zero in the other. */
+#define AHIP_LINALG_EIG 0
+#define AHIP_SYEV_TILE 64
+#define AHIP_SYEV_NSWEEP 30
+#define AHIP_SYEV_OFF_PARTIALS 256
+#define AHIP_SYEV_STATUS_WORDS (4 + 2 * AHIP_SYEV_OFF_PARTIALS)
+int ahip_syev_tile(int dtype, int lower, int64_t batch, int64_t m, const void* A, int64_t a_bs,
+                   int64_t a_rs, int64_t a_cs, void* S, int64_t s_bs, int64_t s_rs, int64_t s_cs,
+                   void* J, int64_t j_bs, int64_t j_rs, int64_t j_cs, void* w, int64_t w_bs,
+                   double tol_scale, void* status, void* info, void* stream);
+int ahip_syev_gather(int dtype, int64_t nb, int64_t step, const void* A, int64_t rs, int64_t cs, void* T,
+                     void* stream);
+int ahip_syev_apply(int dtype, int64_t nb, int64_t step, int64_t rows, const void* X, int64_t x_rs,
+                    int64_t x_cs, const void* J, void* Y, int64_t y_rs, int64_t y_cs, void* stream);
+int ahip_syev_off(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs, void* status, const void* info,
+                  void* stream);
+int ahip_potrf_diag(int dtype, int lower, int64_t nb, void* B, int64_t rs, int64_t cs, int64_t base,
+                    void* info, void* stream);
+int ahip_syev_diag(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs, void* w, void* stream);
+int ahip_scale_cols(int dtype, int64_t rows, int64_t cols, const void* V, int64_t v_rs, int64_t v_cs,
+                    const int64_t* perm, const void* g, const void* h, void* out, int64_t o_rs, int64_t o_cs,
+                    void* stream);
+int ahip_sym_fold(int dtype, int lower, int64_t n, const void* G, int64_t g_rs, int64_t g_cs, void* out,
+                  int64_t o_rs, int64_t o_cs, void* stream);
 /* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
  * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
  * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
