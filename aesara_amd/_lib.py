@@ -209,6 +209,12 @@ SIGNATURES = {
     "ahip_syev_diag": (i32, [i32, i64, vp, i64, i64, vp, vp]),
     "ahip_scale_cols": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp]),
     "ahip_sym_fold": (i32, [i32, i32, i64, vp, i64, i64, vp, i64, i64, vp]),
+    "ahip_gesvj_tile": (i32, [i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64,
+                              vp, i64, vp, vp, vp]),
+    "ahip_gesvj_gram": (i32, [i32, i64, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_gesvj_gram_tile": (i32, [i32, i64, i64, i64, vp, vp, vp, i64, vp]),
+    "ahip_gesvj_done": (i32, [i64, vp, vp, vp]),
+    "ahip_pinv_weights": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
     "ahip_csr_narrow_max": (i32, []),
     "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),

@@ -56,6 +56,9 @@ def linalg_error(code, opname=None):
     calls: ``scipy.linalg.solve_triangular`` / ``solve`` / ``numpy.linalg.inv``; non-finite operands
     as ``scipy``'s ``check_finite``."""
     kind, k = (code >> 32) & 0xFF, 0xFFFFFFFF - (code & 0xFFFFFFFF)
+    if opname == "MatrixPinv" and (kind == NONFINITE or (kind == EIG and k == 0)):
+        # (exec_svd.py) np.linalg.pinv of a NaN, and Jacobi sweeps that ran out
+        return np.linalg.LinAlgError("SVD did not converge")
     if kind == NONFINITE:
         return ValueError("array must not contain infs or NaNs")
     if kind == EIG:
@@ -285,7 +288,12 @@ class LinalgMixin:
             raise ValueError(f"{node.op}: mode {mode!r} (one of {', '.join(QR_MODES)})")
         if A.ndim != 2:
             raise ValueError(f"{node.op}: expected a matrix, got shape {tuple(A.shape)}")
-        (M, N), code = A.shape, dtype_code(dt)
+        return self._la_qr(A, mode)
+
+    def _la_qr(self, A: DevArray, mode):
+        """The outputs of ``np.linalg.qr(A, mode)`` for a float32 / float64 matrix view (also the QR in
+        front of the tall operands of exec_svd.py)."""
+        (M, N), dt, code = A.shape, A.dtype, dtype_code(A.dtype)
         K = min(M, N)
         H = self.alloc((N, M), dt)
         Aw = H.view((M, N), (1, M))

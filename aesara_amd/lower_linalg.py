@@ -16,9 +16,15 @@ to plan ops of the same names with their ``lower``: one operand for the standard
 ``NoneConst``), two for the generalised one, three for the gradient (csrc/eig.hip; executor:
 exec_eig.py).
 
-``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``MatrixPinv``, ``Lstsq``,
-``Expm``, the Lyapunov solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they are refused by
-name like every Op without one.
+``MatrixPinv`` (``nlinalg.pinv``, nlinalg.py:16) lowers to the plan op ``MatrixPinv`` with its
+``hermitian`` (csrc/svd.hip; executor: exec_svd.py).  Its ``L_op`` (:32) is a graph of ``Dot``,
+``identity_like``, transposes and Elemwise over the Op's own output, so ``aesara.grad`` through ``pinv`` —
+and ``matrix_power`` with a negative exponent — needs nothing else.  The singular value decomposition
+computed there never leaves the Op.
+
+``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``Lstsq``, ``Expm``, the Lyapunov
+solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they are refused by name like every Op
+without one.
 
 Registered by ``lower._register_handlers`` like lower_pool.py; every handler cites the reference Op
 it restates.
@@ -38,7 +44,7 @@ def family(name):
 
 
 def register(hip_lower, static_shape, UnsupportedOp):                       # noqa: N803
-    from aesara.tensor.nlinalg import Det, MatrixInverse, QRFull
+    from aesara.tensor.nlinalg import Det, MatrixInverse, MatrixPinv, QRFull
     from aesara.tensor.slinalg import CholeskySolve, Eigvalsh, EigvalshGrad, Solve, SolveTriangular
 
     from .lower_more import _B
@@ -114,3 +120,9 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
         # reference: slinalg.py:493 EigvalshGrad (perform :533 scipy.linalg.eigh(a, b, lower), then
         # v diag(gw) v^T and -v diag(gw w) v^T folded into the named triangle)
         _emit("EigvalshGrad", node, ctx, {"lower": bool(op.lower)})
+
+    @hip_lower.register(MatrixPinv)
+    def _(op, node, ctx):
+        # reference: nlinalg.py:16 MatrixPinv (perform :27 np.linalg.pinv(x, hermitian).astype(x.dtype);
+        # make_node :22 declares the operand's own type, so an integer operand is refused by _emit)
+        _emit("MatrixPinv", node, ctx, {"hermitian": bool(op.hermitian)})

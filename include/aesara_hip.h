@@ -671,6 +671,51 @@ int ahip_scale_cols(int dtype, int64_t rows, int64_t cols, const void* V, int64_
                     void* stream);
 int ahip_sym_fold(int dtype, int lower, int64_t n, const void* G, int64_t g_rs, int64_t g_cs, void* out,
                   int64_t o_rs, int64_t o_cs, void* stream);
+/* ---- K22: singular values by one-sided (Hestenes) Jacobi, under the pseudo-inverse ----------------
+ * the kernels under tensor/nlinalg.py:16 MatrixPinv (np.linalg.pinv).  dtype: AHIP_F32 or AHIP_F64;
+ * (row, col) element strides; extents below 2^30.  The matrix has no more columns than rows (the
+ * caller passes the transposed view otherwise).  The caller owns the tournament and sweep loops;
+ * every dependency between workgroups is a launch boundary and every fold has a fixed order.  The
+ * ordering is K21's circle method, and ahip_syev_apply multiplies the block columns by J.
+ * tol: a pair of columns rotates only if |x_p . x_q| > tol ||x_p|| ||x_q||, tol = AHIP_GESVJ_TOL(rows,
+ * eps) = sqrt(rows) eps — the threshold of LAPACK's gesvj (Demmel and Veselic's scaled test, with
+ * Drmac's sqrt(rows) for the rounding of an inner product of that length).  A zero column never
+ * rotates.  Sweeps end with the first that rotates nothing, at most AHIP_SYEV_NSWEEP.
+ * status: device record of AHIP_GESVJ_STATUS_HEAD + (nb - 1) nb / 2 uint64 words, zeroed by the
+ * caller: [0] done, [1] sweeps counted by gesvj_done, [2] the rotations of the last sweep, [3] the
+ * largest sweep count of gesvj_tile, then one slot per (step, pair): step * nb / 2 + pair.
+ * info: the node's info word of K18; kind AHIP_LINALG_EIG, k = 0: no convergence.
+ *   gesvj_tile:      a batch of rows x cols tiles (cols <= rows <= AHIP_SYEV_TILE), ONE workgroup a
+ *                    tile, X and the accumulated rotations V resident in LDS, one barrier a step (a
+ *                    wave takes a pair, a lane a row; the three sums in double).  Writes W = X V
+ *                    (orthogonal columns of norms sigma), V, and norm2 (cols doubles a tile) if not null.
+ *   gesvj_gram:      P[pair, slab] (contiguous 64 x 64) = C^T C over the AHIP_GESVJ_SLAB rows of the
+ *                    slab, C = [A_p A_q] for pair (p, q) of `step` in a tournament of nb 32-wide column
+ *                    blocks, on the 16x16x4 matrix instructions; slabs = ceil(rows / AHIP_GESVJ_SLAB).
+ *   gesvj_gram_tile: per pair, G = the sum of its slab partials in slab order; two-sided Jacobi on G in
+ *                    LDS under the same scaled threshold |g_pq| > tol sqrt(g_pp g_qq) (rows: the row
+ *                    count tol is taken for); writes J[pair] (64 x 64 row-major) and the tile's
+ *                    rotation count into status slot slot0 + pair with a plain store.
+ *   gesvj_done:      one workgroup: status[2] = the sum of `slots` slots, status[1] += 1, status[0] =
+ *                    no rotation, or *info != 0.
+ *   pinv_weights:    one workgroup: sigma[j] = ||W[:, j]|| in double (or |w[j]| when W is null and the
+ *                    eigenvalues w are given), cutoff = AHIP_PINV_RCOND max sigma in double, d[j] =
+ *                    1 / sigma[j] (1 / w[j]) in the working type where sigma[j] > cutoff, else 0. */
+#define AHIP_GESVJ_SLAB 256
+#define AHIP_GESVJ_STATUS_HEAD 4
+#define AHIP_GESVJ_TOL(rows, eps) (sqrt((double)(rows)) * (eps))
+#define AHIP_PINV_RCOND 1e-15
+int ahip_gesvj_tile(int dtype, int64_t batch, int64_t rows, int64_t cols, const void* X, int64_t x_bs,
+                    int64_t x_rs, int64_t x_cs, void* W, int64_t w_bs, int64_t w_rs, int64_t w_cs, void* V,
+                    int64_t v_bs, int64_t v_rs, int64_t v_cs, double* norm2, int64_t n_bs, void* status,
+                    void* info, void* stream);
+int ahip_gesvj_gram(int dtype, int64_t nb, int64_t step, int64_t rows, const void* A, int64_t rs, int64_t cs,
+                    void* P, void* stream);
+int ahip_gesvj_gram_tile(int dtype, int64_t pairs, int64_t slabs, int64_t rows, const void* P, void* J,
+                         void* status, int64_t slot0, void* stream);
+int ahip_gesvj_done(int64_t slots, void* status, const void* info, void* stream);
+int ahip_pinv_weights(int dtype, int64_t rows, int64_t cols, const void* W, int64_t w_rs, int64_t w_cs,
+                      const void* w, double* sigma, void* d, void* stream);
 /* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
  * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
  * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
