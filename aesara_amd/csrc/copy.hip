@@ -4,7 +4,7 @@
 // tensor/subtensor.py:1454 IncSubtensor (perform :1556), materialisation of DimShuffle views
 // (tensor/c_code/dimshuffle.c), compile/ops.py:149 DeepCopyOp and tensor/basic.py:2142 Join.
 // Views themselves are stride arithmetic on the host and never reach this file.
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
@@ -80,14 +80,6 @@ __global__ __launch_bounds__(256) void fill_kernel(FillArgs f) {
 }
 
 int64_t g_copy_stream_bytes = 96LL << 20;   // copies of at least this many bytes read their source with streaming loads
-
-unsigned stream_grid(int64_t items) {
-  int64_t want = (items + 255) / 256;
-  int64_t cap = (int64_t)ahip_cu_count() * 8;
-  if (want > cap) want = cap;
-  if (want < 1) want = 1;
-  return (unsigned)want;
-}
 
 template <typename T, bool ACC>
 int launch_copy(CopyArgs& a, int vec, hipStream_t s) {

@@ -4,9 +4,9 @@
 // replaces tensor/slinalg.py:446 Eigvalsh and :493 EigvalshGrad (scipy.linalg.eigvalsh / eigh:
 // LAPACK syevr / sygvd).
 //
-// Jacobi with the round-robin ("circle") ordering needs no tridiagonalisation: the m/2 rotations of
-// a step touch disjoint pairs of rows and columns, so a step is two barriers, and the accumulated
-// rotations ARE the eigenvectors the gradient needs.  ahip_syev_tile solves tiles of at most 64 x 64
+// Jacobi with the round-robin ("circle") ordering (jacobi.h) needs no tridiagonalisation: the m/2
+// rotations of a step touch disjoint pairs of rows and columns, so a step is two barriers, and the
+// accumulated rotations ARE the eigenvectors the gradient needs.  ahip_syev_tile solves tiles of at most 64 x 64
 // entirely in LDS, one workgroup a tile.  A larger matrix is a tournament of 32-wide blocks: per
 // step ahip_syev_gather copies every pair of blocks into a 64 x 64 tile, the tile solver returns
 // its rotation matrix J, and ahip_syev_apply multiplies the two block columns of every pair by J on
@@ -15,54 +15,19 @@
 // between workgroups is a launch boundary: no kernel here waits for another workgroup.
 //
 // All matrices are addressed by (row, col) element strides.  Errors travel through the optional
-// info word of K18 (kind AHIP_LINALG_EIG): one atomicMax, never a trap.  Every fold has a fixed
-// order (no float atomics): the same call gives the same bits.
-#include "common.h"
-
-#include <cfloat>
+// info word of K18 (dense.h; kind AHIP_LINALG_EIG).  Every fold has a fixed order (no float
+// atomics): the same call gives the same bits.
+#include "jacobi.h"
 
 namespace {
 
-constexpr int TM = AHIP_SYEV_TILE;          // rows of a tile
-constexpr int BS = TM / 2;                  // rows of a block of the tournament
-constexpr int LD = TM + 1;                  // LDS row pitch: a column walk is conflict-free
-constexpr int NSWEEP = AHIP_SYEV_NSWEEP;
-constexpr int TILE_THREADS = 512;
-constexpr int TILE_WAVES = TILE_THREADS / 64;
 constexpr int PARTIALS = AHIP_SYEV_OFF_PARTIALS;
-constexpr int64_t MAX_N = (int64_t)1 << 30;
 // words of the status record
 constexpr int ST_DONE = 0, ST_SWEEPS = 1, ST_OFF2 = 2, ST_NORM2 = 3, ST_PARTIALS = 4;
 
-inline bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
-
 template <typename F> struct Lim;
-template <> struct Lim<float> {
-  static constexpr double eps = FLT_EPSILON;
-  static constexpr float big = 1e18f;       // theta^2 stays finite below it
-};
-template <> struct Lim<double> {
-  static constexpr double eps = DBL_EPSILON;
-  static constexpr double big = 1e150;
-};
-
-__device__ inline void report(void* info, int64_t k) {
-  if (info != nullptr)
-    atomicMax(static_cast<unsigned long long*>(info),
-              (unsigned long long)AHIP_LINALG_INFO_TAG | ((unsigned long long)AHIP_LINALG_EIG << 32) |
-                  (0xFFFFFFFFull - (unsigned long long)k));
-}
-
-// The circle method for m2 players (m2 even): in step k of m2 - 1, pair 0 is (m2 - 1, k) and pair i
-// is ((k + i) mod (m2 - 1), (k - i) mod (m2 - 1)).  The pairs of a step are disjoint and every two
-// players meet once in m2 - 1 steps.  Returns p < q.
-__device__ inline void rr_pair(int m2, int k, int i, int& p, int& q) {
-  const int r = m2 - 1;
-  const int a = i == 0 ? r : (k + i) % r;
-  const int b = (k - i + r) % r;
-  p = a < b ? a : b;
-  q = a < b ? b : a;
-}
+template <> struct Lim<float> { static constexpr float big = 1e18f; };     // theta^2 stays finite below it
+template <> struct Lim<double> { static constexpr double big = 1e150; };
 
 // sum over a workgroup, the same value in every thread: lanes by shuffles, waves in wave order
 template <int WAVES>
@@ -105,18 +70,18 @@ __device__ inline double tile_sum(const F* S, int m, bool offdiag, double* red) 
 }
 
 // One workgroup a tile.  S and J stay in LDS for the whole solve.  A step: the first m2 / 2 threads
-// take (c, s) of their pair from a_pp, a_qq, a_pq; then the column rotations S <- S G, J <- J G (a
-// wave takes a pair, a lane a row), a barrier, the row rotations S <- G^T S (a lane a column), a
-// barrier.  The norms are accumulated in double whatever F is: the squares of a float32 tile of
-// entries near 1e-19 would be flushed to zero and stop the sweeps early.
+// take (c, s) of their pair from a_pp, a_qq, a_pq; then apply_rotations (jacobi.h).  The norms are
+// accumulated in double whatever F is: the squares of a float32 tile of entries near 1e-19 would be
+// flushed to zero and stop the sweeps early.
 template <typename F>
 __global__ __launch_bounds__(TILE_THREADS) void syev_tile_kernel(TileArgs a) {
   __shared__ F rot_c[BS], rot_s[BS];
   __shared__ int rot_p[BS], rot_q[BS], rot_on[BS];
+  const Rotations<F> rot{rot_c, rot_s, rot_p, rot_q, rot_on};
   __shared__ double red[TILE_WAVES];
   F* S = reinterpret_cast<F*>(eig_lds);
   F* J = S + TM * LD;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = a.m;
+  const int tid = threadIdx.x, m = a.m;
   const int64_t b = blockIdx.x;
   const F* A = static_cast<const F*>(a.A) + b * a.a_bs;
   for (int e = tid; e < m * m; e += TILE_THREADS) {
@@ -130,7 +95,7 @@ __global__ __launch_bounds__(TILE_THREADS) void syev_tile_kernel(TileArgs a) {
   const double norm2 = tile_sum(S, m, false, red);
   // an error already recorded for this node (B not positive definite): the operand is not what
   // it should be, so no sweeps are spent on it and nothing more is reported
-  const bool skip = a.info != nullptr && *static_cast<const unsigned long long*>(a.info) != 0;
+  const bool skip = failed(a.info);
   int sweeps = 0;
   bool conv;
   while (true) {
@@ -156,31 +121,10 @@ __global__ __launch_bounds__(TILE_THREADS) void syev_tile_kernel(TileArgs a) {
             on = false;                        // the exact identity
           }
         }
-        rot_p[tid] = p; rot_q[tid] = q; rot_c[tid] = c; rot_s[tid] = s; rot_on[tid] = on;
+        rot.p[tid] = p; rot.q[tid] = q; rot.c[tid] = c; rot.s[tid] = s; rot.on[tid] = on;
       }
       __syncthreads();
-      for (int i = wave; i < np; i += TILE_WAVES) {
-        if (!rot_on[i] || lane >= m) continue;
-        const int p = rot_p[i], q = rot_q[i];
-        const F c = rot_c[i], s = rot_s[i];
-        F x = S[lane * LD + p], y = S[lane * LD + q];
-        S[lane * LD + p] = c * x - s * y;
-        S[lane * LD + q] = s * x + c * y;
-        x = J[lane * LD + p]; y = J[lane * LD + q];
-        J[lane * LD + p] = c * x - s * y;
-        J[lane * LD + q] = s * x + c * y;
-      }
-      __syncthreads();
-      for (int i = wave; i < np; i += TILE_WAVES) {
-        if (!rot_on[i] || lane >= m) continue;
-        const int p = rot_p[i], q = rot_q[i];
-        const F c = rot_c[i], s = rot_s[i];
-        const F x = S[p * LD + lane], y = S[q * LD + lane];
-        // a_pq = a_qp = 0 exactly: what the angle was chosen for
-        S[p * LD + lane] = lane == q ? F(0) : c * x - s * y;
-        S[q * LD + lane] = lane == p ? F(0) : s * x + c * y;
-      }
-      __syncthreads();
+      apply_rotations(S, J, rot, np, m);
     }
     ++sweeps;
   }
@@ -195,7 +139,7 @@ __global__ __launch_bounds__(TILE_THREADS) void syev_tile_kernel(TileArgs a) {
   if (tid == 0) {
     if (a.status != nullptr)
       atomicMax(static_cast<unsigned long long*>(a.status) + ST_SWEEPS, (unsigned long long)sweeps);
-    if (!conv && !skip) report(a.info, 0);
+    if (!conv && !skip) report(a.info, AHIP_LINALG_EIG, 0);
   }
 }
 
@@ -207,11 +151,6 @@ struct GatherArgs {
   int nb, step;
 };
 AHIP_PTRS_BEGIN(GatherArgs) AHIP_PTR1(A) AHIP_PTR1(T) AHIP_PTRS_END
-
-// row / column of the whole matrix that row / column e of the tile of blocks (p, q) stands for
-__device__ inline int64_t pair_index(int p, int q, int e) {
-  return e < BS ? (int64_t)p * BS + e : (int64_t)q * BS + (e - BS);
-}
 
 template <typename F>
 __global__ __launch_bounds__(256) void syev_gather_kernel(GatherArgs a) {
@@ -232,22 +171,6 @@ struct ApplyArgs {
   int nb, step;
 };
 AHIP_PTRS_BEGIN(ApplyArgs) AHIP_PTR1(X) AHIP_PTR1(J) AHIP_PTR1(Y) AHIP_PTRS_END
-
-template <typename F> struct Mma;
-template <> struct Mma<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ void mma(acc_t& c, float x, float y) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) * 4 + r; }
-};
-template <> struct Mma<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ void mma(acc_t& c, double x, double y) {
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
 
 // Y[:, p|q] = X[:, p|q] J_pair for the pairs of a step: grid (pair, tile of 64 rows), four waves
 // of 16 rows each.  J_pair is staged once in LDS; a wave's 16 x 64 strip of X goes from memory
@@ -339,10 +262,10 @@ __global__ __launch_bounds__(PARTIALS) void syev_off_final_kernel(OffArgs a) {
   }
   if (t == 0) {
     const double off2 = so[0], norm2 = so[0] + sd[0];
-    const bool failed = a.info != nullptr && *static_cast<const unsigned long long*>(a.info) != 0;
+    const bool fail = failed(a.info);
     st[ST_OFF2] = (unsigned long long)__double_as_longlong(off2);
     st[ST_NORM2] = (unsigned long long)__double_as_longlong(norm2);
-    st[ST_DONE] = (!(off2 > a.tol2 * norm2) || failed) ? 1ull : 0ull;
+    st[ST_DONE] = (!(off2 > a.tol2 * norm2) || fail) ? 1ull : 0ull;
   }
 }
 
@@ -372,7 +295,7 @@ __global__ __launch_bounds__(256) void potrf_diag_kernel(PotrfArgs a) {
   for (int j = 0; j < nb; ++j) {
     const F d = S[j][j];
     if (!(d > F(0)) || !isfinite(d)) {          // (the same value in every thread)
-      if (tid == 0) report(a.info, a.base + j + 1);
+      if (tid == 0) report(a.info, AHIP_LINALG_EIG, a.base + j + 1);
       return;
     }
     const F l = sqrt(d);
@@ -466,24 +389,6 @@ __global__ __launch_bounds__(256) void sym_fold_kernel(FoldArgs a) {
   }
 }
 
-unsigned stream_grid(int64_t total) {
-  int64_t cap = (int64_t)ahip_cu_count() * 8;
-  if (cap < 1) cap = 1;
-  const int64_t want = (total + 255) / 256;
-  return (unsigned)(want < cap ? want : cap);
-}
-
-template <typename K>
-int allow_lds(K kernel, size_t lds) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    ahip_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return AHIP_EHIP;
-  }
-  return AHIP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -503,23 +408,8 @@ int ahip_syev_tile(int dtype, int lower, int64_t batch, int64_t m, const void* A
   a.a_bs = a_bs; a.a_rs = a_rs; a.a_cs = a_cs; a.s_bs = s_bs; a.s_rs = s_rs; a.s_cs = s_cs;
   a.j_bs = j_bs; a.j_rs = j_rs; a.j_cs = j_cs; a.w_bs = w_bs;
   a.m = (int)m; a.lower = lower != 0;
-  hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) {
-    const size_t lds = 2 * TM * LD * sizeof(float);
-    a.tol2 = Lim<float>::eps * Lim<float>::eps * tol_scale;
-    AHIP_LAUNCH(syev_tile_kernel<float>, dim3((unsigned)batch), dim3(TILE_THREADS), lds, s, a);
-  } else {
-    const size_t lds = 2 * TM * LD * sizeof(double);      // 65 KiB of the 160: above the default limit
-    static bool allowed = false;
-    if (!allowed) {
-      int rc = allow_lds(syev_tile_kernel<double>, lds);
-      if (rc) return rc;
-      allowed = true;
-    }
-    a.tol2 = Lim<double>::eps * Lim<double>::eps * tol_scale;
-    AHIP_LAUNCH(syev_tile_kernel<double>, dim3((unsigned)batch), dim3(TILE_THREADS), lds, s, a);
-  }
-  return AHIP_OK;
+  a.tol2 = eps_of(dtype) * eps_of(dtype) * tol_scale;
+  return launch_tiles<syev_tile_kernel<float>, syev_tile_kernel<double>>(dtype, batch, a, as_stream(stream));
 }
 
 int ahip_syev_gather(int dtype, int64_t nb, int64_t step, const void* A, int64_t rs, int64_t cs, void* T,
@@ -531,8 +421,7 @@ int ahip_syev_gather(int dtype, int64_t nb, int64_t step, const void* A, int64_t
   GatherArgs a;
   a.A = A; a.T = T; a.rs = rs; a.cs = cs; a.nb = (int)nb; a.step = (int)step;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(syev_gather_kernel<float>, dim3((unsigned)(nb / 2)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(syev_gather_kernel<double>, dim3((unsigned)(nb / 2)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, syev_gather_kernel, dim3((unsigned)(nb / 2)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -549,8 +438,7 @@ int ahip_syev_apply(int dtype, int64_t nb, int64_t step, int64_t rows, const voi
   a.nb = (int)nb; a.step = (int)step;
   const dim3 grid((unsigned)(nb / 2), (unsigned)((rows + TM - 1) / TM));
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(syev_apply_kernel<float>, grid, dim3(256), 0, s, a);
-  else AHIP_LAUNCH(syev_apply_kernel<double>, grid, dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, syev_apply_kernel, grid, dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -561,13 +449,11 @@ int ahip_syev_off(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs, v
   AHIP_REQUIRE(A != nullptr && status != nullptr, "null pointer");
   OffArgs a;
   a.A = A; a.status = status; a.info = info; a.rs = rs; a.cs = cs; a.n = n;
-  const double eps = dtype == AHIP_F32 ? Lim<float>::eps : Lim<double>::eps;
-  a.tol2 = eps * eps;
+  a.tol2 = eps_of(dtype) * eps_of(dtype);
   const int64_t want = (n * n + 2047) / 2048;
   a.parts = (int)(want < PARTIALS ? want : PARTIALS);
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(syev_off_partial_kernel<float>, dim3(a.parts), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(syev_off_partial_kernel<double>, dim3(a.parts), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, syev_off_partial_kernel, dim3(a.parts), dim3(256), 0, s, a);
   AHIP_LAUNCH(syev_off_final_kernel, dim3(1), dim3(PARTIALS), 0, s, a);
   return AHIP_OK;
 }
@@ -582,8 +468,7 @@ int ahip_potrf_diag(int dtype, int lower, int64_t nb, void* B, int64_t rs, int64
   PotrfArgs a;
   a.B = B; a.info = info; a.rs = rs; a.cs = cs; a.base = base; a.nb = (int)nb; a.lower = lower != 0;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(potrf_diag_kernel<float>, dim3(1), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(potrf_diag_kernel<double>, dim3(1), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, potrf_diag_kernel, dim3(1), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -596,8 +481,7 @@ int ahip_syev_diag(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs, 
   a.A = A; a.w = w; a.rs = rs; a.cs = cs; a.n = n;
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(diag_kernel<float>, dim3(grid), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(diag_kernel<double>, dim3(grid), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, diag_kernel, dim3(grid), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -612,8 +496,7 @@ int ahip_scale_cols(int dtype, int64_t rows, int64_t cols, const void* V, int64_
   a.V = V; a.perm = perm; a.g = g; a.h = h; a.out = out;
   a.v_rs = v_rs; a.v_cs = v_cs; a.o_rs = o_rs; a.o_cs = o_cs; a.rows = rows; a.cols = cols;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(scale_cols_kernel<float>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(scale_cols_kernel<double>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, scale_cols_kernel, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -627,8 +510,7 @@ int ahip_sym_fold(int dtype, int lower, int64_t n, const void* G, int64_t g_rs, 
   a.G = G; a.out = out; a.g_rs = g_rs; a.g_cs = g_cs; a.o_rs = o_rs; a.o_cs = o_cs; a.n = n;
   a.lower = lower != 0;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(sym_fold_kernel<float>, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(sym_fold_kernel<double>, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, sym_fold_kernel, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 

@@ -26,7 +26,7 @@
 // done once per call by a one-workgroup kernel into the workspace.
 // Limits: powers of two up to 4096, other lengths up to 2048 (m = 4096): the float64 image of 4096
 // points is 68 KiB of the 160 KiB LDS.  Longer axes need a four-step pass through HBM: AHIP_ENOSUP.
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
@@ -339,17 +339,6 @@ inline int fft_m(int64_t n) {
   return m;
 }
 inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
-template <typename K>
-int allow_lds(K kernel, size_t lds) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    ahip_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return AHIP_EHIP;
-  }
-  return AHIP_OK;
-}
 
 template <typename T, int ITER, int MODE, bool BLUE>
 int launch_fft(const FftArgs& a, hipStream_t s) {

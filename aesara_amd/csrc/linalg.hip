@@ -11,23 +11,12 @@
 // dependency between workgroups is a launch boundary: no kernel here waits for another workgroup.
 //
 // All matrices are addressed by (row, col) element strides.  Errors travel through the optional
-// info word (AHIP_LINALG_* in the header): one atomicMax, never a trap.
-#include "common.h"
+// info word (AHIP_LINALG_* in the header; report of dense.h): one atomicMax, never a trap.
+#include "dense.h"
 
 namespace {
 
 constexpr int NB = AHIP_LINALG_NB;
-
-inline bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
-
-// info word: TAG | kind << 32 | (2^32 - 1 - k).  atomicMax keeps the highest kind and, within a
-// kind, the SMALLEST 0-based index k (what LAPACK's info reports), whatever the order the
-// workgroups and launches meet them in.
-__device__ inline void report(unsigned long long* info, int kind, int64_t k) {
-  if (info != nullptr)
-    atomicMax(info, (unsigned long long)AHIP_LINALG_INFO_TAG | ((unsigned long long)kind << 32) |
-                        (0xFFFFFFFFull - (unsigned long long)k));
-}
 
 // ------------------------------------------------------------------ triangular diagonal block ---
 struct TrsmArgs {
@@ -67,7 +56,7 @@ __global__ __launch_bounds__(64) void trsm_diag_mat_kernel(TrsmArgs a) {
   for (int i = 0; i < nb; ++i) Xs[i][lane] = on ? X[i * a.x_rs + col * a.x_cs] : F(0);
   __syncthreads();
   if (blockIdx.x == 0 && !a.unit && lane < nb && Ts[tri(lane, lane)] == F(0))
-    report(static_cast<unsigned long long*>(a.info), AHIP_LINALG_SINGULAR, a.base + lane);
+    report(a.info, AHIP_LINALG_SINGULAR, a.base + lane);
   if (a.lower) {
     for (int i = 0; i < nb; ++i) {
       F s = Xs[i][lane];
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(64) void trsm_diag_vec_kernel(TrsmArgs a) {
   F x = lane < nb ? X[lane * a.x_rs] : F(0);
   __syncthreads();
   if (!a.unit && lane < nb && Ts[lane][lane] == F(0))
-    report(static_cast<unsigned long long*>(a.info), AHIP_LINALG_SINGULAR, a.base + lane);
+    report(a.info, AHIP_LINALG_SINGULAR, a.base + lane);
   if (a.lower) {
     for (int k = 0; k < nb; ++k) {
       F xk = __shfl(x, k, 64);
@@ -188,7 +177,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void getrf_panel_kernel(PanelArgs a)
     __syncthreads();
     const F pivot = rowj[j];
     const bool zero = pivot == F(0);
-    if (zero && tid == 0) report(static_cast<unsigned long long*>(a.info), AHIP_LINALG_SINGULAR, a.base + j);
+    if (zero && tid == 0) report(a.info, AHIP_LINALG_SINGULAR, a.base + j);
     best = F(-1);
     best_i = j + 1;
     for (int64_t r = j + 1 + tid; r < rows; r += nthreads) {
@@ -306,17 +295,8 @@ __global__ __launch_bounds__(256) void finite_kernel(FiniteArgs a) {
     const F v = X[(e / a.cols) * a.rs + (e % a.cols) * a.cs];
     bad = bad || !isfinite(v);
   }
-  if (bad) report(static_cast<unsigned long long*>(a.info), AHIP_LINALG_NONFINITE, 0);
+  if (bad) report(a.info, AHIP_LINALG_NONFINITE, 0);
 }
-
-unsigned stream_grid(int64_t total) {
-  int64_t cap = (int64_t)ahip_cu_count() * 8;
-  if (cap < 1) cap = 1;
-  const int64_t want = (total + 255) / 256;
-  return (unsigned)(want < cap ? want : cap);
-}
-
-constexpr int64_t MAX_N = (int64_t)1 << 30;
 
 }  // namespace
 
@@ -338,13 +318,11 @@ int ahip_trsm_diag(int dtype, int lower, int unit_diagonal, int64_t nb, int64_t 
   a.nb = (int)nb; a.lower = lower != 0; a.unit = unit_diagonal != 0;
   hipStream_t s = as_stream(stream);
   if (m == 1) {
-    if (dtype == AHIP_F32) AHIP_LAUNCH(trsm_diag_vec_kernel<float>, dim3(1), dim3(64), 0, s, a);
-    else AHIP_LAUNCH(trsm_diag_vec_kernel<double>, dim3(1), dim3(64), 0, s, a);
+    AHIP_LAUNCH_F(dtype, trsm_diag_vec_kernel, dim3(1), dim3(64), 0, s, a);
     return AHIP_OK;
   }
   const unsigned grid = (unsigned)((m + 63) / 64);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(trsm_diag_mat_kernel<float>, dim3(grid), dim3(64), 0, s, a);
-  else AHIP_LAUNCH(trsm_diag_mat_kernel<double>, dim3(grid), dim3(64), 0, s, a);
+  AHIP_LAUNCH_F(dtype, trsm_diag_mat_kernel, dim3(grid), dim3(64), 0, s, a);
   return AHIP_OK;
 }
 
@@ -362,8 +340,7 @@ int ahip_getrf_panel(int dtype, int64_t rows, int64_t nb, void* A, int64_t a_rs,
   hipStream_t s = as_stream(stream);
   // one thread per row up to the largest workgroup: a short panel pays for the barriers of few waves only
   const unsigned threads = (unsigned)(rows >= PANEL_THREADS ? PANEL_THREADS : (rows + 63) / 64 * 64);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(getrf_panel_kernel<float>, dim3(1), dim3(threads), 0, s, a);
-  else AHIP_LAUNCH(getrf_panel_kernel<double>, dim3(1), dim3(threads), 0, s, a);
+  AHIP_LAUNCH_F(dtype, getrf_panel_kernel, dim3(1), dim3(threads), 0, s, a);
   return AHIP_OK;
 }
 
@@ -380,8 +357,7 @@ int ahip_laswp(int dtype, int64_t nrows, int64_t ncols, void* B, int64_t b_rs, i
   a.skip0 = skip0; a.skiplen = skiplen; a.k0 = (int)k0; a.k1 = (int)k1;
   const unsigned grid = (unsigned)((ncols + 255) / 256);
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(laswp_kernel<float>, dim3(grid), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(laswp_kernel<double>, dim3(grid), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, laswp_kernel, dim3(grid), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -393,8 +369,7 @@ int ahip_lu_det(int dtype, int64_t n, const void* LU, int64_t rs, int64_t cs, co
   DetArgs a;
   a.LU = LU; a.piv = piv; a.out = out; a.rs = rs; a.cs = cs; a.n = n;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(lu_det_kernel<float>, dim3(1), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(lu_det_kernel<double>, dim3(1), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, lu_det_kernel, dim3(1), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -406,8 +381,7 @@ int ahip_mirror_triangle(int dtype, int lower, int64_t n, void* A, int64_t rs, i
   MirrorArgs a;
   a.A = A; a.rs = rs; a.cs = cs; a.n = n; a.lower = lower != 0;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(mirror_kernel<float>, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(mirror_kernel<double>, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, mirror_kernel, dim3(stream_grid(n * n)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -420,8 +394,7 @@ int ahip_check_finite(int dtype, int64_t rows, int64_t cols, const void* X, int6
   FiniteArgs a;
   a.X = X; a.info = info; a.rs = rs; a.cs = cs; a.rows = rows; a.cols = cols;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(finite_kernel<float>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(finite_kernel<double>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, finite_kernel, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 

@@ -26,7 +26,7 @@
 // 16 bytes or less in flight per lane): pool_fwd_tile_kernel for windows that
 // tile a 2-d image exactly, pool_grad_disjoint_kernel for gradients of non-overlapping windows.
 // Both meet the values in the general kernels' order and give their bits.
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
@@ -380,7 +380,6 @@ bool small(const PoolArgs& a) {   // every flat index (and the stride of the loo
   return elements(a, a.X) < lim && elements(a, a.O) < lim;
 }
 
-bool float_dtype(int dtype) { return dtype == AHIP_F32 || dtype == AHIP_F64; }
 
 template <typename T, int WV, bool ISMAX>
 int launch_fwd_wv(PoolArgs& a, bool nt, hipStream_t s) {

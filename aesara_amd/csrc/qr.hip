@@ -13,16 +13,13 @@
 // info word: non-finite input gives non-finite output.  No float atomics: every fold has a fixed
 // order (lane-strided partial sums, a shuffle tree inside the wave, the waves in order from LDS), so
 // equal input gives equal bits.
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
 constexpr int NB = AHIP_LINALG_NB;
 constexpr int PANEL_THREADS = 1024;
 constexpr int PANEL_WAVES = PANEL_THREADS / 64;
-constexpr int64_t MAX_N = (int64_t)1 << 30;
-
-inline bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
 
 // ------------------------------------------------------------------ panel ----------------------
 struct Geqr2Args {
@@ -39,8 +36,9 @@ AHIP_PTRS_BEGIN(Geqr2Args) AHIP_PTR1(A) AHIP_PTR1(tau) AHIP_PTR1(V) AHIP_PTRS_EN
 template <typename F>
 __device__ inline F nanmax(F a, F b) { return (b > a || b != b) ? b : a; }
 
+// (lane 0's sum of a down-shuffle tree, broadcast: not the butterfly order of dense.h's wave_sum)
 template <typename F>
-__device__ inline F wave_sum(F v) {
+__device__ inline F wave_sum_down(F v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return __shfl(v, 0, 64);
 }
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void geqr2_panel_kernel(Geqr2Args a)
         const F q = col[r * a.rs] / scale;
         ss += q * q;
       }
-      ss = wave_sum(ss);
+      ss = wave_sum_down(ss);
       if (lane == 0) fold[wave] = ss;                                   // (fold was read before the last barrier)
       __syncthreads();
       if (tid == 0) {
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void geqr2_panel_kernel(Geqr2Args a)
         F w = F(0);
 #pragma unroll 8
         for (int64_t r = j + 1 + lane; r < rows; r += 64) w += vcol[r * a.v_rs] * ac[r * a.rs];
-        w = wave_sum(w);
+        w = wave_sum_down(w);
         const F top = ac[j * a.rs];                                     // (same address for all lanes)
         const F tw = tj * (top + w);
 #pragma unroll 8
@@ -201,13 +199,6 @@ __global__ __launch_bounds__(256) void extract_r_kernel(ExtractArgs a) {
   }
 }
 
-unsigned stream_grid(int64_t total) {
-  int64_t cap = (int64_t)ahip_cu_count() * 8;
-  if (cap < 1) cap = 1;
-  const int64_t want = (total + 255) / 256;
-  return (unsigned)(want < cap ? want : cap);
-}
-
 }  // namespace
 
 extern "C" {
@@ -231,8 +222,7 @@ int ahip_geqr2_panel(int dtype, int64_t rows, int64_t nb, void* A, int64_t a_rs,
   if (waves > PANEL_WAVES) waves = PANEL_WAVES;
   if (waves < 1) waves = 1;
   const unsigned threads = (unsigned)(waves * 64);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(geqr2_panel_kernel<float>, dim3(1), dim3(threads), 0, s, a);
-  else AHIP_LAUNCH(geqr2_panel_kernel<double>, dim3(1), dim3(threads), 0, s, a);
+  AHIP_LAUNCH_F(dtype, geqr2_panel_kernel, dim3(1), dim3(threads), 0, s, a);
   return AHIP_OK;
 }
 
@@ -245,8 +235,7 @@ int ahip_larft(int dtype, int64_t nb, const void* G, int64_t g_rs, int64_t g_cs,
   LarftArgs a;
   a.G = G; a.tau = tau; a.T = T; a.g_rs = g_rs; a.g_cs = g_cs; a.t_rs = t_rs; a.t_cs = t_cs; a.nb = (int)nb;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(larft_kernel<float>, dim3(1), dim3(64), 0, s, a);
-  else AHIP_LAUNCH(larft_kernel<double>, dim3(1), dim3(64), 0, s, a);
+  AHIP_LAUNCH_F(dtype, larft_kernel, dim3(1), dim3(64), 0, s, a);
   return AHIP_OK;
 }
 
@@ -260,8 +249,7 @@ int ahip_qr_extract_r(int dtype, int64_t rows, int64_t cols, const void* A, int6
   ExtractArgs a;
   a.A = A; a.R = R; a.a_rs = a_rs; a.a_cs = a_cs; a.r_rs = r_rs; a.r_cs = r_cs; a.rows = rows; a.cols = cols;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(extract_r_kernel<float>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
-  else AHIP_LAUNCH(extract_r_kernel<double>, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, extract_r_kernel, dim3(stream_grid(rows * cols)), dim3(256), 0, s, a);
   return AHIP_OK;
 }
 

@@ -20,7 +20,7 @@
 // The two multinomial kernels run one lane per row of pvals, sequentially over the outcomes: the
 // running sum is a double added in the reference's order (a parallel prefix sum would round
 // differently and move a draw across a boundary).
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
@@ -203,7 +203,6 @@ __global__ __launch_bounds__(256) void choice_kernel(MultiArgs a) {
   }
 }
 
-bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
 
 int fill_multi(MultiArgs& a, int odtype, const void* unis, int64_t u_s, int64_t nb_multi, int64_t nb_outcomes,
                int64_t n_samples, void* out) {
@@ -245,8 +244,7 @@ int ahip_mrg_uniform(int dtype, const void* rstate_in, void* rstate_out, int64_t
   a.c = jmax > 0 ? (jmax + parts - 1) / parts : 1;
   const dim3 grid((unsigned)((lanes + 255) / 256));
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(mrg_uniform_kernel<float>, grid, dim3(256), 0, s, a);
-  else AHIP_LAUNCH(mrg_uniform_kernel<double>, grid, dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, mrg_uniform_kernel, grid, dim3(256), 0, s, a);
   return AHIP_OK;
 }
 

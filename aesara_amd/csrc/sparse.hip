@@ -16,17 +16,15 @@
 // Safety: a row range is used only if 0 <= start <= end <= nnz and an entry only if its index is
 // in [0, minor); anything else is recorded in the info word (AHIP_SPARSE_* in the header, one
 // atomicMax) and the entry / row is skipped.  Nothing traps.
-#include "common.h"
+#include "dense.h"
 
 namespace {
 
-inline bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
 constexpr int64_t MAX_EXT = (int64_t)1 << 31;   // int32 indices: every extent and nnz stay below
 
 __device__ inline void report(unsigned long long* info, int what) {
   if (info != nullptr)
-    atomicMax(info, (unsigned long long)AHIP_LINALG_INFO_TAG |
-                        ((unsigned long long)AHIP_SPARSE_MALFORMED << 32) | (unsigned long long)what);
+    atomicMax(info, info_word(AHIP_SPARSE_MALFORMED, (unsigned long long)what));
 }
 
 // [s, e) of row r, or false (recorded) when it is not a range inside [0, nnz]
@@ -49,14 +47,6 @@ __device__ inline int checked_index(const int* indices, int64_t k, int64_t minor
     return -1;
   }
   return j;
-}
-
-// sum over the 64 lanes in a fixed order (xor butterfly: every lane ends with the same bits)
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 constexpr int WAVES = 4;          // waves (= rows) per workgroup of the row kernels
@@ -396,8 +386,7 @@ int ahip_csr_spmm(int dtype, int64_t M, int64_t minor, int64_t ncols, int64_t nn
   hipStream_t s = as_stream(stream);
   SpmmArgs a{data, perm, indices, indptr, B, out, info, M, minor, ncols, nnz, b_rs, b_cs, o_rs, o_cs};
   if (ncols <= NARROW_MAX) {
-    if (dtype == AHIP_F32) AHIP_LAUNCH(spmm_narrow_kernel<float>, dim3(row_blocks(M)), dim3(64 * WAVES), 0, s, a);
-    else AHIP_LAUNCH(spmm_narrow_kernel<double>, dim3(row_blocks(M)), dim3(64 * WAVES), 0, s, a);
+    AHIP_LAUNCH_F(dtype, spmm_narrow_kernel, dim3(row_blocks(M)), dim3(64 * WAVES), 0, s, a);
     return AHIP_OK;
   }
   const int vec = dtype == AHIP_F32 ? 4 : 2;
@@ -425,11 +414,9 @@ int ahip_csr_sddmm(int dtype, int64_t M, int64_t minor, int64_t ncols, int64_t n
   SddmmArgs a{indices, indptr, G, B, out, info, M, minor, ncols, nnz, g_rs, g_cs, b_rs, b_cs};
   const dim3 grid(row_blocks(M)), block(64 * WAVES);
   if (ncols <= SDDMM_LANE_MAX) {
-    if (dtype == AHIP_F32) AHIP_LAUNCH(sddmm_lane_kernel<float>, grid, block, 0, s, a);
-    else AHIP_LAUNCH(sddmm_lane_kernel<double>, grid, block, 0, s, a);
+    AHIP_LAUNCH_F(dtype, sddmm_lane_kernel, grid, block, 0, s, a);
   } else {
-    if (dtype == AHIP_F32) AHIP_LAUNCH(sddmm_wave_kernel<float>, grid, block, 0, s, a);
-    else AHIP_LAUNCH(sddmm_wave_kernel<double>, grid, block, 0, s, a);
+    AHIP_LAUNCH_F(dtype, sddmm_wave_kernel, grid, block, 0, s, a);
   }
   return AHIP_OK;
 }
@@ -441,8 +428,7 @@ int ahip_csr_to_dense(int dtype, int64_t M, int64_t minor, int64_t nnz, const vo
   if (M == 0 || minor == 0) return AHIP_OK;
   DenseArgs a{data, indices, indptr, D, nullptr, nullptr, info, M, minor, nnz, d_rs, d_cs};
   const dim3 grid((unsigned)((M + 255) / 256)), block(256);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(to_dense_kernel<float>, grid, block, 0, as_stream(stream), a);
-  else AHIP_LAUNCH(to_dense_kernel<double>, grid, block, 0, as_stream(stream), a);
+  AHIP_LAUNCH_F(dtype, to_dense_kernel, grid, block, 0, as_stream(stream), a);
   return AHIP_OK;
 }
 
@@ -454,8 +440,7 @@ int ahip_csr_mul_dense(int dtype, int64_t M, int64_t minor, int64_t nnz, const v
   if (M == 0 || nnz == 0) return AHIP_OK;
   DenseArgs a{data, indices, indptr, const_cast<void*>(D), out, nullptr, info, M, minor, nnz, d_rs, d_cs};
   const dim3 grid(row_blocks(M)), block(64 * WAVES);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(mul_dense_kernel<float>, grid, block, 0, as_stream(stream), a);
-  else AHIP_LAUNCH(mul_dense_kernel<double>, grid, block, 0, as_stream(stream), a);
+  AHIP_LAUNCH_F(dtype, mul_dense_kernel, grid, block, 0, as_stream(stream), a);
   return AHIP_OK;
 }
 
@@ -466,8 +451,7 @@ int ahip_dense_count_rows(int dtype, int64_t M, int64_t minor, const void* D, in
   if (M == 0) return AHIP_OK;
   DenseArgs a{nullptr, nullptr, nullptr, const_cast<void*>(D), nullptr, counts, nullptr, M, minor, 0, d_rs, d_cs};
   const dim3 grid(row_blocks(M)), block(64 * WAVES);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(dense_count_kernel<float>, grid, block, 0, as_stream(stream), a);
-  else AHIP_LAUNCH(dense_count_kernel<double>, grid, block, 0, as_stream(stream), a);
+  AHIP_LAUNCH_F(dtype, dense_count_kernel, grid, block, 0, as_stream(stream), a);
   return AHIP_OK;
 }
 
@@ -478,8 +462,7 @@ int ahip_dense_fill_csr(int dtype, int64_t M, int64_t minor, int64_t nnz, const 
   if (M == 0 || nnz == 0) return AHIP_OK;
   DenseArgs a{nullptr, nullptr, indptr, const_cast<void*>(D), data, indices, nullptr, M, minor, nnz, d_rs, d_cs};
   const dim3 grid(row_blocks(M)), block(64 * WAVES);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(dense_fill_kernel<float>, grid, block, 0, as_stream(stream), a);
-  else AHIP_LAUNCH(dense_fill_kernel<double>, grid, block, 0, as_stream(stream), a);
+  AHIP_LAUNCH_F(dtype, dense_fill_kernel, grid, block, 0, as_stream(stream), a);
   return AHIP_OK;
 }
 

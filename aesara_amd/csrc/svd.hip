@@ -9,64 +9,26 @@
 // not to the matrix, which is what keeps the small singular values — the ones a pseudo-inverse
 // divides by — as accurate as the large ones.  ahip_gesvj_tile solves tiles of at most 64 x 64
 // entirely in LDS, one workgroup a tile, ONE barrier a step.  Above 64 columns 32-wide column blocks
-// play the tournament of eig.hip: per step ahip_gesvj_gram forms the 64 x 64 Gram matrix of every
-// pair of blocks on the matrix instructions (slab partials, no atomics), ahip_gesvj_gram_tile folds
-// the partials, diagonalises each Gram matrix by two-sided rotations under the same scaled threshold
-// and returns its rotation matrix J, and ahip_syev_apply (eig.hip) multiplies the block columns of A
-// and V by J.  ahip_gesvj_done sums a sweep's rotation counts; ahip_pinv_weights turns column norms
+// play a tournament in the round-robin ordering of jacobi.h: per step ahip_gesvj_gram forms the
+// 64 x 64 Gram matrix of every pair of blocks on the matrix instructions (slab partials, no atomics),
+// ahip_gesvj_gram_tile folds the partials, diagonalises each Gram matrix by two-sided rotations
+// under the same scaled threshold and returns its rotation matrix J, and ahip_syev_apply (a kernel
+// of eig.hip) multiplies the block columns of A and V by J.  ahip_gesvj_done sums a sweep's rotation counts; ahip_pinv_weights turns column norms
 // (or eigenvalues) into the reciprocals the pseudo-inverse scales by.
 //
 // Every dependency between workgroups is a launch boundary: no kernel here waits for another
 // workgroup.  Every fold has a fixed order (no float atomics): the same call gives the same bits.
-// Errors travel through the info word of K18 (kind AHIP_LINALG_EIG, k = 0).
-#include "common.h"
+// Errors travel through the info word of K18 (dense.h; kind AHIP_LINALG_EIG, k = 0).
+#include "jacobi.h"
 
-#include <cfloat>
 #include <cmath>
 
 namespace {
 
-constexpr int TM = AHIP_SYEV_TILE;          // rows / columns of a tile
-constexpr int BS = TM / 2;                  // columns of a block of the tournament
-constexpr int LD = TM + 1;                  // LDS row pitch: a column walk is conflict-free
-constexpr int NSWEEP = AHIP_SYEV_NSWEEP;
-constexpr int TILE_THREADS = 512;
-constexpr int TILE_WAVES = TILE_THREADS / 64;
 constexpr int SLAB = AHIP_GESVJ_SLAB;       // rows of A behind one partial Gram matrix
 constexpr int HEAD = AHIP_GESVJ_STATUS_HEAD;
-constexpr int64_t MAX_N = (int64_t)1 << 30;
 // words of the status record
 constexpr int ST_DONE = 0, ST_SWEEPS = 1, ST_ROTATIONS = 2, ST_TILE_SWEEPS = 3;
-
-inline bool float_dtype(int dt) { return dt == AHIP_F32 || dt == AHIP_F64; }
-inline double eps_of(int dt) { return dt == AHIP_F32 ? (double)FLT_EPSILON : (double)DBL_EPSILON; }
-
-__device__ inline void report(void* info, int64_t k) {
-  if (info != nullptr)
-    atomicMax(static_cast<unsigned long long*>(info),
-              (unsigned long long)AHIP_LINALG_INFO_TAG | ((unsigned long long)AHIP_LINALG_EIG << 32) |
-                  (0xFFFFFFFFull - (unsigned long long)k));
-}
-
-__device__ inline bool failed(const void* info) {
-  return info != nullptr && *static_cast<const unsigned long long*>(info) != 0;
-}
-
-// the circle method of eig.hip: step k of m2 - 1 (m2 even) pairs (m2 - 1, k) and ((k + i) mod
-// (m2 - 1), (k - i) mod (m2 - 1)); returns p < q
-__device__ inline void rr_pair(int m2, int k, int i, int& p, int& q) {
-  const int r = m2 - 1;
-  const int a = i == 0 ? r : (k + i) % r;
-  const int b = (k - i + r) % r;
-  p = a < b ? a : b;
-  q = a < b ? b : a;
-}
-
-// sum over a wave, the same bits in every lane: a butterfly, whose order is fixed
-__device__ inline double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // sum of small counts over a workgroup, the same value in every thread
 template <int WAVES>
@@ -81,7 +43,7 @@ __device__ inline int block_count(int v, int* red) {
 }
 
 // (c, s) of the rotation that makes two columns of squared norms al, be and inner product ga
-// orthogonal — the formulas of syev_tile_kernel with theta = (be - al) / (2 ga), in double
+// orthogonal: theta = (be - al) / (2 ga), t the smaller root of t^2 + 2 theta t - 1, in double
 __device__ inline void rotation(double al, double be, double ga, double& c, double& s) {
   const double theta = (be - al) / (2.0 * ga);
   const double at = fabs(theta);
@@ -177,27 +139,11 @@ __global__ __launch_bounds__(TILE_THREADS) void gesvj_tile_kernel(TileArgs a) {
   if (tid == 0) {
     if (a.status != nullptr)
       atomicMax(static_cast<unsigned long long*>(a.status) + ST_TILE_SWEEPS, (unsigned long long)sweeps);
-    if (!conv && !skip) report(a.info, 0);
+    if (!conv && !skip) report(a.info, AHIP_LINALG_EIG, 0);
   }
 }
 
 // ------------------------------------------------------------------ the Gram matrices ----------
-template <typename F> struct Mma;
-template <> struct Mma<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ void mma(acc_t& c, float x, float y) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) * 4 + r; }
-};
-template <> struct Mma<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ void mma(acc_t& c, double x, double y) {
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
-
 struct GramArgs {
   const void* A;   // rows x (32 nb)
   void* P;         // (pair, slab) contiguous 64 x 64 partial Gram matrices
@@ -205,11 +151,6 @@ struct GramArgs {
   int nb, step, slabs;
 };
 AHIP_PTRS_BEGIN(GramArgs) AHIP_PTR1(A) AHIP_PTR1(P) AHIP_PTRS_END
-
-// column of the whole matrix that column e of the pair of blocks (p, q) stands for
-__device__ inline int64_t pair_index(int p, int q, int e) {
-  return e < BS ? (int64_t)p * BS + e : (int64_t)q * BS + (e - BS);
-}
 
 // the ten 16 x 16 fragments (fi <= fj) of the upper triangle of a 64 x 64 symmetric matrix, by rows
 __host__ __device__ constexpr int frag(int fi, int fj) { return fi * 4 - fi * (fi - 1) / 2 + fj - fi; }
@@ -286,18 +227,18 @@ struct GramTileArgs {
 AHIP_PTRS_BEGIN(GramTileArgs) AHIP_PTR1(P) AHIP_PTR1(J) AHIP_PTR1(status) AHIP_PTRS_END
 
 // One workgroup a pair: G = sum of the slab partials in slab order, then two-sided Jacobi on G in
-// LDS in the schedule of syev_tile_kernel (column rotations of G and J, a barrier, row rotations, a
-// barrier) — but a pair rotates only if |g_pq| > tol sqrt(g_pp g_qq), and the sweeps end with the
-// first that rotates nothing.  A norm-wise stop would leave the couplings of columns of small norm
+// LDS (apply_rotations of jacobi.h on a full tile) — a pair rotates only if |g_pq| > tol sqrt(g_pp
+// g_qq), and the sweeps end with the first that rotates nothing.  A norm-wise stop would leave the couplings of columns of small norm
 // unresolved.  A zero column of A is a zero row and column of G: it never rotates.
 template <typename F>
 __global__ __launch_bounds__(TILE_THREADS) void gesvj_gram_tile_kernel(GramTileArgs a) {
   __shared__ F rot_c[BS], rot_s[BS];
   __shared__ int rot_p[BS], rot_q[BS], rot_on[BS];
+  const Rotations<F> rot{rot_c, rot_s, rot_p, rot_q, rot_on};
   __shared__ int red[TILE_WAVES];
   F* S = reinterpret_cast<F*>(svd_lds);
   F* J = S + TM * LD;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const F* P = static_cast<const F*>(a.P) + (int64_t)blockIdx.x * a.slabs * TM * TM;
   for (int e = tid; e < TM * TM; e += TILE_THREADS) {
     F g = F(0);
@@ -324,30 +265,10 @@ __global__ __launch_bounds__(TILE_THREADS) void gesvj_gram_tile_kernel(GramTileA
           c = (F)cd; s = (F)sd;
           ++mine;
         }
-        rot_p[tid] = p; rot_q[tid] = q; rot_c[tid] = c; rot_s[tid] = s; rot_on[tid] = on;
+        rot.p[tid] = p; rot.q[tid] = q; rot.c[tid] = c; rot.s[tid] = s; rot.on[tid] = on;
       }
       __syncthreads();
-      for (int i = wave; i < BS; i += TILE_WAVES) {
-        if (!rot_on[i]) continue;
-        const int p = rot_p[i], q = rot_q[i];
-        const F c = rot_c[i], s = rot_s[i];
-        F x = S[lane * LD + p], y = S[lane * LD + q];
-        S[lane * LD + p] = c * x - s * y;
-        S[lane * LD + q] = s * x + c * y;
-        x = J[lane * LD + p]; y = J[lane * LD + q];
-        J[lane * LD + p] = c * x - s * y;
-        J[lane * LD + q] = s * x + c * y;
-      }
-      __syncthreads();
-      for (int i = wave; i < BS; i += TILE_WAVES) {
-        if (!rot_on[i]) continue;
-        const int p = rot_p[i], q = rot_q[i];
-        const F c = rot_c[i], s = rot_s[i];
-        const F x = S[p * LD + lane], y = S[q * LD + lane];
-        S[p * LD + lane] = lane == q ? F(0) : c * x - s * y;
-        S[q * LD + lane] = lane == p ? F(0) : s * x + c * y;
-      }
-      __syncthreads();
+      apply_rotations(S, J, rot, BS, TM);
     }
     const int count = block_count<TILE_WAVES>(mine, red);
     total += count;
@@ -453,17 +374,6 @@ __global__ __launch_bounds__(WT_THREADS) void pinv_weights_kernel(WeightArgs a) 
   }
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t lds) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    ahip_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return AHIP_EHIP;
-  }
-  return AHIP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -485,21 +395,7 @@ int ahip_gesvj_tile(int dtype, int64_t batch, int64_t rows, int64_t cols, const 
   a.v_bs = v_bs; a.v_rs = v_rs; a.v_cs = v_cs; a.n_bs = n_bs;
   a.tol = AHIP_GESVJ_TOL(rows, eps_of(dtype));
   a.rows = (int)rows; a.cols = (int)cols;
-  hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) {
-    const size_t lds = 2 * TM * LD * sizeof(float);
-    AHIP_LAUNCH(gesvj_tile_kernel<float>, dim3((unsigned)batch), dim3(TILE_THREADS), lds, s, a);
-  } else {
-    const size_t lds = 2 * TM * LD * sizeof(double);      // 65 KiB of the 160: above the default limit
-    static bool allowed = false;
-    if (!allowed) {
-      int rc = allow_lds(gesvj_tile_kernel<double>, lds);
-      if (rc) return rc;
-      allowed = true;
-    }
-    AHIP_LAUNCH(gesvj_tile_kernel<double>, dim3((unsigned)batch), dim3(TILE_THREADS), lds, s, a);
-  }
-  return AHIP_OK;
+  return launch_tiles<gesvj_tile_kernel<float>, gesvj_tile_kernel<double>>(dtype, batch, a, as_stream(stream));
 }
 
 int ahip_gesvj_gram(int dtype, int64_t nb, int64_t step, int64_t rows, const void* A, int64_t rs, int64_t cs,
@@ -515,8 +411,7 @@ int ahip_gesvj_gram(int dtype, int64_t nb, int64_t step, int64_t rows, const voi
   AHIP_REQUIRE(a.slabs <= 65535, "gesvj_gram: %lld rows are more than 65535 slabs", (long long)rows);
   const dim3 grid((unsigned)(nb / 2), (unsigned)a.slabs);
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(gesvj_gram_kernel<float>, grid, dim3(256), 0, s, a);
-  else AHIP_LAUNCH(gesvj_gram_kernel<double>, grid, dim3(256), 0, s, a);
+  AHIP_LAUNCH_F(dtype, gesvj_gram_kernel, grid, dim3(256), 0, s, a);
   return AHIP_OK;
 }
 
@@ -530,21 +425,8 @@ int ahip_gesvj_gram_tile(int dtype, int64_t pairs, int64_t slabs, int64_t rows, 
   GramTileArgs a;
   a.P = P; a.J = J; a.status = status; a.slot0 = slot0; a.slabs = (int)slabs;
   a.tol = AHIP_GESVJ_TOL(rows, eps_of(dtype));
-  hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) {
-    const size_t lds = 2 * TM * LD * sizeof(float);
-    AHIP_LAUNCH(gesvj_gram_tile_kernel<float>, dim3((unsigned)pairs), dim3(TILE_THREADS), lds, s, a);
-  } else {
-    const size_t lds = 2 * TM * LD * sizeof(double);
-    static bool allowed = false;
-    if (!allowed) {
-      int rc = allow_lds(gesvj_gram_tile_kernel<double>, lds);
-      if (rc) return rc;
-      allowed = true;
-    }
-    AHIP_LAUNCH(gesvj_gram_tile_kernel<double>, dim3((unsigned)pairs), dim3(TILE_THREADS), lds, s, a);
-  }
-  return AHIP_OK;
+  return launch_tiles<gesvj_gram_tile_kernel<float>, gesvj_gram_tile_kernel<double>>(dtype, pairs, a,
+                                                                                       as_stream(stream));
 }
 
 int ahip_gesvj_done(int64_t slots, void* status, const void* info, void* stream) {
@@ -566,8 +448,7 @@ int ahip_pinv_weights(int dtype, int64_t rows, int64_t cols, const void* W, int6
   WeightArgs a;
   a.W = W; a.w = w; a.sigma = sigma; a.d = d; a.w_rs = w_rs; a.w_cs = w_cs; a.rows = rows; a.cols = cols;
   hipStream_t s = as_stream(stream);
-  if (dtype == AHIP_F32) AHIP_LAUNCH(pinv_weights_kernel<float>, dim3(1), dim3(WT_THREADS), 0, s, a);
-  else AHIP_LAUNCH(pinv_weights_kernel<double>, dim3(1), dim3(WT_THREADS), 0, s, a);
+  AHIP_LAUNCH_F(dtype, pinv_weights_kernel, dim3(1), dim3(WT_THREADS), 0, s, a);
   return AHIP_OK;
 }
 

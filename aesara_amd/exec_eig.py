@@ -96,6 +96,19 @@ class EigMixin:
         return Cm, True, L
 
     # ------------------------------------------------------------------ Jacobi --------
+    def _jacobi_apply(self, code, nb, step, rows, src: DevArray, dst: DevArray, ld, Jt: DevArray, transposed=False):
+        """``dst[:, p|q] = src[:, p|q] J`` for the pairs of a tournament step (``ahip_syev_apply``), on
+        ``rows`` rows of two row-major workspaces of pitch ``ld``; ``transposed``: on their transposed
+        views, which is ``dst[p|q, :] = J^T src[p|q, :]``."""
+        rs, cs = (1, ld) if transposed else (ld, 1)
+        self._launch("ahip_syev_apply", (code, nb, step, rows, _VP(src.ptr), rs, cs, _VP(Jt.ptr),
+                                         _VP(dst.ptr), rs, cs, self._stream()))
+
+    def _jacobi_done(self, status: DevArray):
+        """The done word of a status record, read on the host: ONE word a sweep.  While a launch list
+        is recorded the read raises HostReadInReplay: such a plan runs eagerly."""
+        return int(self.host_array(status.view((1,), (1,)))[0]) != 0
+
     def _eig_jacobi(self, Cm: DevArray, lower, want_v, info):
         """(``w`` unsorted, ``V`` or None) of the symmetric ``Cm``, of which only the triangle ``lower``
         names is read: the diagonal of ``V^T Cm V`` and the accumulated rotations."""
@@ -127,11 +140,8 @@ class EigMixin:
         while True:
             self._launch("ahip_syev_off", (code, n_pad, _VP(W0.ptr), n_pad, 1, _VP(status.ptr), info,
                                            self._stream()))
-            if self.dry_run:
-                done = sweeps >= 1          # (a dry run has no values: it shows the launches of one sweep)
-            else:
-                # one host read a sweep; while a launch list is recorded it raises HostReadInReplay
-                done = int(self.host_array(status.view((1,), (1,)))[0]) != 0
+            # (a dry run has no values: it shows the launches of one sweep)
+            done = sweeps >= 1 if self.dry_run else self._jacobi_done(status)
             if done:
                 break
             if sweeps == NSWEEP:
@@ -142,15 +152,11 @@ class EigMixin:
                 self._launch("ahip_syev_tile", (code, 1, pairs, TILE, _VP(T.ptr), tt, TILE, 1, None, 0, 0, 0,
                                                 _VP(Jt.ptr), tt, TILE, 1, None, 0, 1.0 / (nb - 1),
                                                 _VP(status.ptr), None, self._stream()))
-                # A <- A J into the other workspace, then A <- J^T A back: the same kernel on the
-                # transposed views
-                self._launch("ahip_syev_apply", (code, nb, step, n_pad, _VP(W0.ptr), n_pad, 1, _VP(Jt.ptr),
-                                                 _VP(W1.ptr), n_pad, 1, self._stream()))
-                self._launch("ahip_syev_apply", (code, nb, step, n_pad, _VP(W1.ptr), 1, n_pad, _VP(Jt.ptr),
-                                                 _VP(W0.ptr), 1, n_pad, self._stream()))
+                # A <- A J into the other workspace, then A <- J^T A back
+                self._jacobi_apply(code, nb, step, n_pad, W0, W1, n_pad, Jt)
+                self._jacobi_apply(code, nb, step, n_pad, W1, W0, n_pad, Jt, transposed=True)
                 if want_v:
-                    self._launch("ahip_syev_apply", (code, nb, step, n_pad, _VP(V0.ptr), n_pad, 1, _VP(Jt.ptr),
-                                                     _VP(V1.ptr), n_pad, 1, self._stream()))
+                    self._jacobi_apply(code, nb, step, n_pad, V0, V1, n_pad, Jt)
                     V0, V1 = V1, V0
             sweeps += 1
         self._launch("ahip_syev_diag", (code, n, _VP(W0.ptr), n_pad, 1, _VP(w.ptr), self._stream()))

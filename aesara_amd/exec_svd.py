@@ -82,15 +82,13 @@ class SvdMixin:
                 self._launch("ahip_gesvj_gram_tile", (code, pairs, slabs, rows, _VP(P.ptr), _VP(Jt.ptr),
                                                       _VP(status.ptr), step * pairs, self._stream()))
                 for S0, S1, n in ((A0, A1, rows), (V0, V1, k_pad)):
-                    self._launch("ahip_syev_apply", (code, nb, step, n, _VP(S0.ptr), k_pad, 1, _VP(Jt.ptr),
-                                                     _VP(S1.ptr), k_pad, 1, self._stream()))
+                    self._jacobi_apply(code, nb, step, n, S0, S1, k_pad, Jt)
                 A0, A1, V0, V1 = A1, A0, V1, V0
             sweeps += 1
             self._launch("ahip_gesvj_done", (slots, _VP(status.ptr), info, self._stream()))
             if self.dry_run:
                 break                       # (a dry run has no values: it shows the launches of one sweep)
-            # one host read a sweep; while a launch list is recorded it raises HostReadInReplay
-            if int(self.host_array(status.view((1,), (1,)))[0]) != 0:
+            if self._jacobi_done(status):
                 break
             if sweeps == NSWEEP:
                 raise np.linalg.LinAlgError("SVD did not converge")
