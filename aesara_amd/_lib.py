@@ -215,6 +215,10 @@ SIGNATURES = {
     "ahip_gesvj_gram_tile": (i32, [i32, i64, i64, i64, vp, vp, vp, i64, vp]),
     "ahip_gesvj_done": (i32, [i64, vp, vp, vp]),
     "ahip_pinv_weights": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "ahip_expm_tile": (i32, [i32, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp]),
+    "ahip_expm_norm1": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
+    "ahip_expm_combine": (i32, [i32, i64, i32, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, C.c_double,
+                                C.c_double, vp, vp]),
     "ahip_csr_narrow_max": (i32, []),
     "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),

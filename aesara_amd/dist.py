@@ -78,6 +78,7 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   "MrgUniform", "MultinomialFromUniform", "ChoiceFromUniform",
                   # (a factorisation couples every row and column of its matrix: not batch-splittable)
                   "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det", "QR", "Eigvalsh", "EigvalshGrad", "MatrixPinv",
+                  "Expm", "ExpmGrad",
                   # (the members of a sparse value address each other: splitting `data` alone means nothing)
                   "StructuredDot", "SparseDot", "SampledDot", "DenseFromSparse", "SparseFromDense", "SpSum",
                   "MulSD"}

@@ -22,9 +22,13 @@ exec_eig.py).
 and ``matrix_power`` with a negative exponent — needs nothing else.  The singular value decomposition
 computed there never leaves the Op.
 
-``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``Lstsq``, ``Expm``, the Lyapunov
-solvers, ``TensorInv`` / ``TensorSolve``) have no handler: they are refused by name like every Op
-without one.
+``Expm`` and ``ExpmGrad`` (``slinalg.expm`` and its ``grad``, slinalg.py:595 / :631) lower to plan ops of the
+same names without parameters: one operand, and two for the gradient (the matrix and the output's
+gradient).  ``make_node`` declares the operand's own dtype for the result, so an integer operand reaches
+``_emit`` and is refused there by name (csrc/expm.hip; executor: exec_expm.py).
+
+``Cholesky`` and the other decompositions (``Eigh``, ``Eig``, ``SVD``, ``Lstsq``, the Lyapunov solvers,
+``TensorInv`` / ``TensorSolve``) have no handler: they are refused by name like every Op without one.
 
 Registered by ``lower._register_handlers`` like lower_pool.py; every handler cites the reference Op
 it restates.
@@ -45,7 +49,8 @@ def family(name):
 
 def register(hip_lower, static_shape, UnsupportedOp):                       # noqa: N803
     from aesara.tensor.nlinalg import Det, MatrixInverse, MatrixPinv, QRFull
-    from aesara.tensor.slinalg import CholeskySolve, Eigvalsh, EigvalshGrad, Solve, SolveTriangular
+    from aesara.tensor.slinalg import (CholeskySolve, Eigvalsh, EigvalshGrad, Expm, ExpmGrad, Solve,
+                                       SolveTriangular)
 
     from .lower_more import _B
 
@@ -126,3 +131,15 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
         # reference: nlinalg.py:16 MatrixPinv (perform :27 np.linalg.pinv(x, hermitian).astype(x.dtype);
         # make_node :22 declares the operand's own type, so an integer operand is refused by _emit)
         _emit("MatrixPinv", node, ctx, {"hermitian": bool(op.hermitian)})
+
+    @hip_lower.register(Expm)
+    def _(op, node, ctx):
+        # reference: slinalg.py:595 Expm (perform :617 scipy.linalg.expm(A); make_node :603 declares the
+        # operand's own dtype, so an integer operand is refused by _emit)
+        _emit("Expm", node, ctx, {})
+
+    @hip_lower.register(ExpmGrad)
+    def _(op, node, ctx):
+        # reference: slinalg.py:631 ExpmGrad (perform :654: eig(A), inv(V) and the divided differences of
+        # exp; the executor takes the block-triangular route to the same Frechet derivative)
+        _emit("ExpmGrad", node, ctx, {})

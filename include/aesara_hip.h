@@ -716,6 +716,33 @@ int ahip_gesvj_gram_tile(int dtype, int64_t pairs, int64_t slabs, int64_t rows, 
 int ahip_gesvj_done(int64_t slots, void* status, const void* info, void* stream);
 int ahip_pinv_weights(int dtype, int64_t rows, int64_t cols, const void* W, int64_t w_rs, int64_t w_cs,
                       const void* w, double* sigma, void* d, void* stream);
+/* ---- K23: the matrix exponential by scaling and squaring ---------------------------------------
+ * the kernels under tensor/slinalg.py:595 Expm (scipy.linalg.expm) and :631 ExpmGrad (the top-right
+ * block of expm([[A^T, G], [0, A^T]]), assembled by the caller).  dtype: AHIP_F32 or AHIP_F64.
+ * Higham's 2005 algorithm: ||A||_1 picks the Pade degree m in {3, 5, 7, 9, 13} and the scaling s (the
+ * float64 thresholds for both dtypes); r_m(2^-s A) by one LU solve, then s squarings.  Nothing fails
+ * and there is no info word: a norm that is not finite gives s = 0 and a non-finite result.
+ * status: AHIP_EXPM_STATUS_WORDS int64 words a matrix: [0] the bits of the double ||A||_1, [1] m, [2] s.
+ *   expm_tile:    a batch of n x n matrices (n <= AHIP_EXPM_TILE_F32 / _F64), (batch, row, col) element
+ *                 strides, ONE workgroup a matrix and the whole algorithm in LDS: seven matrices at
+ *                 pitch limit + 1, every product on the 16x16x4 matrix instructions over extents padded
+ *                 with zeros to a multiple of 16, the 2^-s scaling exact, LU with partial pivoting and
+ *                 both substitutions over all n right-hand sides, the squarings between two buffers.
+ *                 status may be null.
+ *   expm_norm1:   the blocked path's first step: colsum[j] = sum_i |A[i, j]| in double (64 columns a
+ *                 workgroup, a fixed order), then one workgroup folds them and writes the status record.
+ *   expm_combine: out = sum_{i < nops} c_i X_i + d I on contiguous n x n matrices (nops <= 4; out may be
+ *                 one of the X_i): the linear combinations of the Pade polynomials and, with one operand,
+ *                 the 2^-s scaling. */
+#define AHIP_EXPM_TILE_F32 64
+#define AHIP_EXPM_TILE_F64 48
+#define AHIP_EXPM_STATUS_WORDS 3
+int ahip_expm_tile(int dtype, int64_t batch, int64_t n, const void* A, int64_t a_bs, int64_t a_rs, int64_t a_cs,
+                   void* out, int64_t o_bs, int64_t o_rs, int64_t o_cs, void* status, void* stream);
+int ahip_expm_norm1(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs, double* colsum, void* status,
+                    void* stream);
+int ahip_expm_combine(int dtype, int64_t n, int nops, const void* x0, double c0, const void* x1, double c1,
+                      const void* x2, double c2, const void* x3, double c3, double d, void* out, void* stream);
 /* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
  * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
  * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
