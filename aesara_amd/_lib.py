@@ -219,6 +219,8 @@ SIGNATURES = {
     "ahip_expm_norm1": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
     "ahip_expm_combine": (i32, [i32, i64, i32, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, C.c_double,
                                 C.c_double, vp, vp]),
+    "ahip_convolve_ws_bytes": (sz, [i32, i64, i64, i64, i64]),
+    "ahip_convolve": (i32, [i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, sz, vp]),
     "ahip_csr_narrow_max": (i32, []),
     "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),

@@ -79,6 +79,8 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   # (a factorisation couples every row and column of its matrix: not batch-splittable)
                   "SolveTriangular", "CholeskySolve", "Solve", "MatrixInverse", "Det", "QR", "Eigvalsh", "EigvalshGrad", "MatrixPinv",
                   "Expm", "ExpmGrad",
+                  # (every output of a convolution reads a window of both operands)
+                  "Convolve",
                   # (the members of a sparse value address each other: splitting `data` alone means nothing)
                   "StructuredDot", "SparseDot", "SampledDot", "DenseFromSparse", "SparseFromDense", "SpSum",
                   "MulSD"}

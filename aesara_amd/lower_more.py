@@ -530,6 +530,27 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
         _fft("IRFFT", node, ctx, node.inputs[0].type.ndim - 1)
 
     # ---------------------------------------------------------------------------------------
+    from aesara.tensor.math import Convolve
+
+    @hip_lower.register(Convolve)
+    def _(op, node, ctx):
+        # reference: tensor/math.py:3005 Convolve (perform :3062 np.convolve(a, v, mode); make_node :3034
+        # declares upcast(a, v)): both operands go to that dtype through the cast Elemwise, so a
+        # float32 / int64 pair runs in float64 -> csrc/convolve.hip, one launch for the three modes
+        from .exec_convolve import DTYPES, MODES
+        b = B(ctx)
+        odt = str(node.outputs[0].type.dtype)
+        dts = [str(i.type.dtype) for i in node.inputs]
+        if odt not in DTYPES or any(d not in DTYPES for d in dts):
+            raise UnsupportedOp(f"Convolve has no HIP lowering for operands of dtypes {dts} giving {odt} (bool, "
+                                "complex and float16 operands stay out: float32 / float64 and the 8- to 64-bit "
+                                "integers only)")
+        if op.mode not in MODES:
+            raise UnsupportedOp(f"Convolve has no HIP lowering for mode = {op.mode!r} (one of {', '.join(MODES)})")
+        ins = [b.cast(ctx.vid(i), odt) for i in node.inputs]
+        ctx.vmap[node.outputs[0]] = ctx.raw("Convolve", ins, odt, [None], {"mode": str(op.mode)})
+
+    # ---------------------------------------------------------------------------------------
     from aesara.tensor.sort import TopKOp
 
     @hip_lower.register(TopKOp)

@@ -743,6 +743,22 @@ int ahip_expm_norm1(int dtype, int64_t n, const void* A, int64_t rs, int64_t cs,
                     void* stream);
 int ahip_expm_combine(int dtype, int64_t n, int nops, const void* x0, double c0, const void* x1, double c1,
                       const void* x2, double c2, const void* x3, double c3, double d, void* out, void* stream);
+/* ---- K24: 1-D convolution ------------------------------------------------------------------------
+ * the kernel under tensor/math.py:3005 Convolve (perform :3062 np.convolve(a, v, mode)).  dtype: AHIP_F32,
+ * AHIP_F64 or one of AHIP_I8 .. AHIP_U64 (integers wrap around like NumPy's; AHIP_BOOL is refused).
+ * a: m elements at element stride sa, v: n elements at element stride sv (any sign: the pointers name
+ * element 0), m >= n >= 1 — the caller swaps.  With full[j] = sum_k v[k] a[j - k], j in [0, m + n - 1), the
+ * call writes out[i] = full[lo + i] for i in [0, len) (contiguous): full is (0, m + n - 1), valid
+ * (n - 1, m - n + 1), same ((n - 1) / 2, m).  A direct LDS-tiled sliding window: 256 threads a tile of
+ * AHIP_CONVOLVE_TILE_OUT outputs, taps staged AHIP_CONVOLVE_TAP_CHUNK at a time, only the taps a tile can
+ * touch.  With fewer than 256 tiles the taps are split S ways (S from m, n, lo, len alone) into the caller's
+ * workspace [S][len], folded in split order: no atomics, the same bits on every call.
+ * ahip_convolve_ws_bytes: the bytes that workspace needs (0: no split, ws may be null). */
+#define AHIP_CONVOLVE_TILE_OUT 2048
+#define AHIP_CONVOLVE_TAP_CHUNK 256
+size_t ahip_convolve_ws_bytes(int dtype, int64_t m, int64_t n, int64_t lo, int64_t len);
+int ahip_convolve(int dtype, const void* a, int64_t m, int64_t sa, const void* v, int64_t n, int64_t sv, int64_t lo,
+                  int64_t len, void* out, void* ws, size_t ws_bytes, void* stream);
 /* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
  * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
  * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
