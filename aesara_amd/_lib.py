@@ -221,6 +221,7 @@ SIGNATURES = {
                                 C.c_double, vp, vp]),
     "ahip_convolve_ws_bytes": (sz, [i32, i64, i64, i64, i64]),
     "ahip_convolve": (i32, [i32, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, sz, vp]),
+    "ahip_images2neibs": (i32, [i32, vp, p_i64, p_i64, p_i64, vp, vp]),
     "ahip_csr_narrow_max": (i32, []),
     "ahip_csr_spmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]),
     "ahip_csr_sddmm": (i32, [i32, i64, i64, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),

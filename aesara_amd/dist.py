@@ -81,6 +81,8 @@ _VIEW_REP_ONLY = {"AdvancedSubtensor1", "AdvancedIncSubtensor1",
                   "Expm", "ExpmGrad",
                   # (every output of a convolution reads a window of both operands)
                   "Convolve",
+                  # (a patch reads rows and columns of one image; its grid comes from host vectors)
+                  "Images2Neibs",
                   # (the members of a sparse value address each other: splitting `data` alone means nothing)
                   "StructuredDot", "SparseDot", "SampledDot", "DenseFromSparse", "SparseFromDense", "SpSum",
                   "MulSD"}

@@ -551,6 +551,19 @@ def register(hip_lower, static_shape, UnsupportedOp):                       # no
         ctx.vmap[node.outputs[0]] = ctx.raw("Convolve", ins, odt, [None], {"mode": str(op.mode)})
 
     # ---------------------------------------------------------------------------------------
+    from aesara.tensor.nnet.neighbours import Images2Neibs
+
+    @hip_lower.register(Images2Neibs)
+    def _(op, node, ctx):
+        # reference: tensor/nnet/neighbours.py:23 Images2Neibs(mode)(ten4, neib_shape, neib_step) (perform :194):
+        # neib_shape / neib_step stay graph inputs (host integer vectors at run time, like the ws / stride / pad
+        # of lower_pool.py); the Op moves elements, so every dtype of a plan passes -> csrc/neibs.hip
+        from .exec_neibs import MODES
+        if op.mode not in MODES:
+            raise UnsupportedOp(f"Images2Neibs has no HIP lowering for mode = {op.mode!r} (one of {', '.join(MODES)})")
+        ctx.emit("Images2Neibs", node, {"mode": str(op.mode)})
+
+    # ---------------------------------------------------------------------------------------
     from aesara.tensor.sort import TopKOp
 
     @hip_lower.register(TopKOp)

@@ -759,6 +759,21 @@ int ahip_expm_combine(int dtype, int64_t n, int nops, const void* x0, double c0,
 size_t ahip_convolve_ws_bytes(int dtype, int64_t m, int64_t n, int64_t lo, int64_t len);
 int ahip_convolve(int dtype, const void* a, int64_t m, int64_t sa, const void* v, int64_t n, int64_t sv, int64_t lo,
                   int64_t len, void* out, void* ws, size_t ws_bytes, void* stream);
+/* ---- K25: sliding-window patches -------------------------------------------------------------------
+ * the kernel under tensor/nnet/neighbours.py:23 Images2Neibs (perform :194).  dtype: any AHIP_* code; only its
+ * item size matters.  x: an image of shape[4] = (N, C, H, W) at element strides[4] (any sign).  geo[12] =
+ * (r, c, step_r, step_c, grid_r, grid_c, off_r, off_c, wrap, band, tile, pitch).  The call writes the contiguous
+ * matrix out[N C grid_r grid_c][r c]:
+ *   out[b + grid_c (a + grid_r (s + C n))][i c + j] = x[n, s, a step_r + i + off_r, b step_c + j + off_c],
+ * zero outside the image, or with both indices wrapped once (wrap != 0; H >= r and W >= c then).  off_r, off_c <= 0
+ * and the grid tell the five modes of the Op apart.  One workgroup stages the image rows of `band` patch rows
+ * (or, band = 1, of `tile` patch columns of one patch row; tile = grid_c otherwise) in LDS at a row pitch of
+ * `pitch` elements and writes them out as 16-byte words; (rows (band - 1) min(step_r, r) + r) pitch itemsize
+ * must not exceed AHIP_NEIBS_LDS_BYTES, pitch is a multiple of 16 / itemsize and covers 16 / itemsize - 1 +
+ * (tile - 1) step_c + c columns.  band = 0: the patch does not fit, one thread an element.  No atomics. */
+#define AHIP_NEIBS_LDS_BYTES 32768
+int ahip_images2neibs(int dtype, const void* x, const int64_t* shape, const int64_t* strides, const int64_t* geo,
+                      void* out, void* stream);
 /* ---- K20: sparse operands (CSR view; float32 / float64 data, int32 indices / indptr) -----------
  * the kernels under aesara/sparse/basic.py StructuredDot (:3424), Dot (:3920), StructuredDotGradCSR /
  * CSC, DenseFromSparse, SparseFromDense, SpSum and MulSD.  A value is (data[nnz],
