@@ -197,6 +197,8 @@ SIGNATURES = {
     "ahip_lu_det": (i32, [i32, i64, vp, i64, i64, vp, vp, vp]),
     "ahip_mirror_triangle": (i32, [i32, i32, i64, vp, i64, i64, vp]),
     "ahip_check_finite": (i32, [i32, i64, i64, vp, i64, i64, vp, vp]),
+    "ahip_lu_tile_max": (i32, []),
+    "ahip_lu_tile": (i32, [i32, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),
     "ahip_geqr2_panel": (i32, [i32, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_larft": (i32, [i32, i64, vp, i64, i64, vp, vp, i64, i64, vp]),
     "ahip_qr_extract_r": (i32, [i32, i64, i64, vp, i64, i64, vp, i64, i64, vp]),

@@ -170,15 +170,45 @@ class EigMixin:
     def _op_Eigvalsh(self, node, args):
         """reference: slinalg.py:476 Eigvalsh.perform (scipy.linalg.eigvalsh(a, b, lower)): ascending
         eigenvalues of ``a x = w b x``; ``b`` absent for the standard problem."""
+        if node.params.get("batched"):
+            return [self._eig_stack(node, args)]
         ops, dt = self._eig_operands(node, args)
+        return [self._eigvalsh(ops, bool(node.params["lower"]))]
+
+    def _eigvalsh(self, ops, lower):
         A, b = ops[0], (ops[1] if len(ops) > 1 else None)
         if A.shape[0] == 0:
-            return [self.alloc((0,), dt)]
+            return self.alloc((0,), A.dtype)
         info = self._la_info()
         self._eig_checked(ops, info)
-        Cm, lo, _ = self._eig_reduce(A, b, bool(node.params["lower"]), info)
+        Cm, lo, _ = self._eig_reduce(A, b, lower, info)
         w, _ = self._eig_jacobi(Cm, lo, False, info)
-        return [self._sort(None, [w, np.int64(0)], False)[0]]
+        return self._sort(None, [w, np.int64(0)], False)[0]
+
+    def _eig_stack(self, node, args):
+        """The standard problem on every matrix of a ``[T, n, n]`` stack (a ``batched`` node of
+        scan_rewrite.batch_map_step): up to ``TILE`` rows ONE ``ahip_syev_tile`` launch with batch = T and one
+        sort of the rows of the ``[T, n]`` result, the single-matrix route per matrix above."""
+        A, dt = self._la_stack(node, args)
+        T, n = A.shape[0], A.shape[1]
+        lower = bool(node.params["lower"])
+        if T == 0 or n == 0:
+            return self.alloc((T, n), dt)
+        if n > TILE:
+            return self._la_each(A, self.alloc((T, n), dt), lambda M: self._eigvalsh([M], lower))
+        info = self._la_info()
+        # (check_finite over the stack as ONE matrix of T n rows: a stack whose leading dimensions do not
+        # fold is copied first)
+        Af = A if A.strides[0] == n * A.strides[1] else self.materialize(A)
+        self._la_check_finite(Af.view((T * n, n), Af.strides[1:]), info)
+        status = self.alloc((STATUS_WORDS,), "int64")
+        self.fill_zero(status)
+        self.eig_status = status
+        w = self.alloc((T, n), dt)
+        self._launch("ahip_syev_tile", (dtype_code(dt), int(lower), T, n, _VP(A.ptr), A.strides[0], A.strides[1],
+                                        A.strides[2], None, 0, 0, 0, None, 0, 0, 0, _VP(w.ptr), n, 1.0,
+                                        _VP(status.ptr), info, self._stream()))
+        return self._sort(None, [w, np.int64(1)], False)[0]
 
     def _op_EigvalshGrad(self, node, args):
         """reference: slinalg.py:533 EigvalshGrad.perform: ``w, v = scipy.linalg.eigh(a, b, lower)``,

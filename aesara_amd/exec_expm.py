@@ -114,11 +114,30 @@ class ExpmMixin:
     # ------------------------------------------------------------------ the Ops -------
     def _op_Expm(self, node, args):
         """reference: slinalg.py:617 Expm.perform (scipy.linalg.expm(A))."""
+        if node.params.get("batched"):
+            return [self._expm_stack(node, args)]
         (A,), dt = self._float_operands(node, args)
         self._expm_square(node, A)
         if A.shape[0] == 0:
             return [self.alloc((0, 0), dt)]
         return [self._expm(A)]
+
+    def _expm_stack(self, node, args):
+        """``expm`` of every matrix of a ``[T, n, n]`` stack (a ``batched`` node of scan_rewrite.batch_map_step):
+        ONE ``ahip_expm_tile`` launch with batch = T inside ``TILE_ROWS``, the single-matrix route per matrix
+        above."""
+        (A,), dt = self._float_operands(node, args)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise np.linalg.LinAlgError("Last 2 dimensions of the array must be square")
+        T, n = A.shape[0], A.shape[1]
+        out = self.alloc((T, n, n), dt)
+        if out.size == 0:
+            return out
+        if n > TILE_ROWS[dt]:
+            return self._la_each(A, out, self._expm)
+        self._launch("ahip_expm_tile", (dtype_code(dt), T, n, _VP(A.ptr), A.strides[0], A.strides[1], A.strides[2],
+                                        _VP(out.ptr), n * n, n, 1, None, self._stream()))
+        return out
 
     def _op_ExpmGrad(self, node, args):
         """reference: slinalg.py:654 ExpmGrad.perform; here the top-right block of

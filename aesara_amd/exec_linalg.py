@@ -36,6 +36,7 @@ from .exec_common import *  # noqa: F401,F403
 from .exec_common import (_I64, _VP, _i64arr, _Kernels, _FakeBuf, _CAST_SCALARS, _prod, _Arena, _os, _time)  # noqa: F401
 
 NB = 64                       # AHIP_LINALG_NB: rows of a diagonal block / columns of a panel
+LU_TILE = 64                  # AHIP_LU_TILE: rows of a matrix of the one-launch stack kernel
 INFO_TAG = 1 << 62            # AHIP_LINALG_INFO_TAG
 SINGULAR, NONFINITE = 2, 3    # AHIP_LINALG_SINGULAR / _NONFINITE
 EIG = 0                       # AHIP_LINALG_EIG (kind 1 is the sparse kernels', exec_sparse.py)
@@ -243,28 +244,71 @@ class LinalgMixin:
         self._la_lu_solve(LU, piv, X)
         return [out]
 
-    def _op_MatrixInverse(self, node, args):
-        """reference: nlinalg.py:124 MatrixInverse.perform (np.linalg.inv): ``Solve`` with B = I."""
-        (A,), dt = self._la_operands(node, args)
-        n = A.shape[0]
+    def _la_inverse(self, A: DevArray):
+        n, dt = A.shape[0], A.dtype
         LU, piv = self._la_factor(A, "gen", False, self._la_info())
         out = self.alloc((n, n), dt)
         self.fill_zero(out)
         if n:
             self.copy_into(out.view((n,), (n + 1,)), self._one(dt))
         self._la_lu_solve(LU, piv, out)
-        return [out]
+        return out
 
-    def _op_Det(self, node, args):
-        """reference: nlinalg.py:210 Det.perform (np.linalg.det): the sign of the interchanges times
-        the diagonal of U; a singular matrix gives 0 (no info word), a 0 x 0 matrix 1."""
-        (A,), dt = self._la_operands(node, args)
-        n = A.shape[0]
+    def _la_det(self, A: DevArray):
+        n, dt = A.shape[0], A.dtype
         LU, piv = self._la_factor(A, "gen", False, None)
         out = self.alloc((), dt)
         self._launch("ahip_lu_det", (dtype_code(dt), n, _VP(LU.ptr), n, 1, _VP(piv.ptr), _VP(out.ptr),
                                      self._stream()))
-        return [out]
+        return out
+
+    def _op_MatrixInverse(self, node, args):
+        """reference: nlinalg.py:124 MatrixInverse.perform (np.linalg.inv): ``Solve`` with B = I."""
+        if node.params.get("batched"):
+            return [self._la_stack_lu(node, args, True)]
+        (A,), dt = self._la_operands(node, args)
+        return [self._la_inverse(A)]
+
+    def _op_Det(self, node, args):
+        """reference: nlinalg.py:210 Det.perform (np.linalg.det): the sign of the interchanges times
+        the diagonal of U; a singular matrix gives 0 (no info word), a 0 x 0 matrix 1."""
+        if node.params.get("batched"):
+            return [self._la_stack_lu(node, args, False)]
+        (A,), dt = self._la_operands(node, args)
+        return [self._la_det(A)]
+
+    # ------------------------------------------------------------------ stacks --------
+    def _la_stack(self, node, args):
+        """The ``[T, n, n]`` operand of a ``batched`` node (scan_rewrite.batch_map_step: a map over
+        small matrices restated over the whole sequence)."""
+        (A,), dt = self._float_operands(node, args[:1])
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError(f"{node.op}: expected a stack of square matrices, got shape {tuple(A.shape)}")
+        return A, dt
+
+    def _la_each(self, A: DevArray, out: DevArray, one):
+        """``out[t] = one(A[t])`` on the host: the stack's matrices are beyond the one-launch kernels."""
+        item = tuple(out.shape[1:]) or (1,)
+        for t in range(A.shape[0]):
+            res = one(A.view(A.shape[1:], A.strides[1:], A.offset + t * A.strides[0]))
+            self.copy_into(out.view(item, contiguous_strides(item), out.offset + t * out.strides[0]),
+                           res.view(item, contiguous_strides(item)))
+        return out
+
+    def _la_stack_lu(self, node, args, want_inv):
+        """``MatrixInverse`` / ``Det`` of every matrix of a stack: ONE launch (``ahip_lu_tile``, every
+        matrix resident in LDS) up to ``LU_TILE`` rows, the single-matrix route per matrix above."""
+        A, dt = self._la_stack(node, args)
+        T, n = A.shape[0], A.shape[1]
+        out = self.alloc((T, n, n) if want_inv else (T,), dt)
+        if out.size == 0:
+            return out
+        if n > LU_TILE:
+            return self._la_each(A, out, self._la_inverse if want_inv else self._la_det)
+        self._launch("ahip_lu_tile", (dtype_code(dt), T, n, _VP(A.ptr), A.strides[0], A.strides[1], A.strides[2],
+                                      _VP(out.ptr) if want_inv else None, None if want_inv else _VP(out.ptr),
+                                      self._la_info() if want_inv else None, self._stream()))
+        return out
 
     # ------------------------------------------------------------------ QR ------------
     def _qr_apply(self, V: DevArray, T: DevArray, Cm: DevArray, W: DevArray, W2: DevArray):

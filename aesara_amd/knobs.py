@@ -71,6 +71,9 @@ _def("MRG_PARTS", 0, int, "pieces a stream's run of MrgUniform is cut into by ju
 _def("SCAN_PERSIST", 1, int, "Scan loops as ONE persistent kernel where the class allows")
 _def("ROWS_BYTES_CAP_GB", 0.0, float, "bytes a whole-sequence evaluation of a Scan without recurrence may allocate before "
      "its rows go in blocks (GiB; 0: a quarter of the free device memory)")
+_def("MAP_LINALG", 1, int, "a map (Scan without recurrence) over Det / MatrixInverse / Eigvalsh / Expm of small matrices is "
+     "restated as ONE batched node on the whole stack (0: the step loop on the launch list; tools/batched_linalg_probe.py "
+     "measures both)")
 _def("COOP", 0, int, "persistent kernels through hipLaunchCooperativeKernel (launch-time size check)")
 _def("SCAN_ROWS", None, str, "rows x waves geometry of the vector-state persistent kernel")
 _def("SCAN_WAVES", 4, int, "waves per workgroup of the vector-state persistent kernel")

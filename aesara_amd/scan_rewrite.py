@@ -25,6 +25,7 @@ from typing import Dict, List
 
 import numpy as np
 
+from . import knobs
 from .plan import Node, Plan
 
 
@@ -1047,6 +1048,8 @@ def hoist_sequence_only(plan: Plan, seq_inputs: List[int], invariant: set):
 
 
 _BATCH_ALIAS = ("ScalarFromTensor", "TensorFromScalar", "ViewOp", "DeepCopyOp")
+# the dense Ops whose executors take a [T, n, n] stack (``batched``: exec_linalg / exec_eig / exec_expm)
+_BATCH_LINALG = ("Det", "MatrixInverse", "Eigvalsh", "Expm")
 
 
 def batch_map_step(plan: Plan, n_seqs: int):
@@ -1070,7 +1073,12 @@ def batch_map_step(plan: Plan, n_seqs: int):
       pairs are distinct); on a step value with invariant indices: one more leading slice;
     * ``Gemv(y, alpha, A, x_t, beta)`` with an invariant matrix: ``X @ A.T`` (``Dot22Scalar`` / ``Gemm``);
     * ``Alloc(v_t, *shape)`` / ``Reshape(v_t, shape)`` / ``SpecifyShape(v_t, *shape)`` with an invariant
-      shape: the same node with T in front of the shape.
+      shape: the same node with T in front of the shape;
+    * ``Det(a_t)`` / ``MatrixInverse(a_t)`` / ``Expm(a_t)`` / ``Eigvalsh(a_t)`` (the standard problem, no
+      ``b``) of a step matrix: the same plan op on the ``[T, n, n]`` stack with ``batched: True`` — one
+      launch of the LDS-resident tile kernels for small matrices (switch ``MAP_LINALG``).  ``Solve``,
+      ``SolveTriangular``, ``CholeskySolve``, ``Eigvalsh`` with ``b``, the ``*Grad`` Ops, ``MatrixPinv`` and
+      ``QR`` have no such form: the step stays a loop.
 
     Returns ``{"plan": Plan(inputs = sequences + the other step-plan inputs), "outs": n}``."""
     V = plan.vars
@@ -1248,6 +1256,10 @@ def batch_map_step(plan: Plan, n_seqs: int):
             step.add(o0)
             bp.nodes.append(Node("Alloc", [get(n.inputs[0]), T_()] + [get(i) for i in n.inputs[1:]], [get(o0)],
                                  dict(n.params)))
+        elif n.op in _BATCH_LINALG and len(n.inputs) == 1 and knobs.get("MAP_LINALG"):
+            # (one operand: an Eigvalsh with ``b`` has two and stays a loop)
+            step.add(o0)
+            bp.nodes.append(Node(n.op, [get(n.inputs[0])], [get(o0)], dict(n.params, batched=True)))
         else:
             return None
     outs = []

@@ -598,6 +598,21 @@ int ahip_lu_det(int dtype, int64_t n, const void* LU, int64_t rs, int64_t cs, co
 int ahip_mirror_triangle(int dtype, int lower, int64_t n, void* A, int64_t rs, int64_t cs, void* stream);
 int ahip_check_finite(int dtype, int64_t rows, int64_t cols, const void* X, int64_t rs, int64_t cs,
                       void* info, void* stream);
+/* ---- K18t: LU of a stack of small matrices in one launch ---------------------------------------
+ * MatrixInverse / Det of K18 on a [batch, n, n] operand, n <= AHIP_LU_TILE (= ahip_lu_tile_max()):
+ * the same algorithm (partial pivoting, the lowest row wins a tie; det folded in lu_det's order; the
+ * inverse by both substitutions on the columns of P I), every matrix resident in LDS from its one
+ * load to its one store.  n <= AHIP_LU_TILE_WAVE: one wavefront a matrix, four a workgroup; above:
+ * one workgroup a matrix, two barriers a column.  A: (batch, row, col) element strides of any sign.
+ *   inv: [batch, n, n] contiguous or null; det: [batch] or null (one of them at least).
+ *   A zero pivot: det gets the exact 0 it multiplies to; with inv, AHIP_LINALG_SINGULAR is recorded
+ *   in info with k = the matrix's index in the batch (the smallest one wins) and that matrix's
+ *   inverse is NaN — nothing divides by a zero pivot.  n == 0: det = 1. */
+#define AHIP_LU_TILE 64
+#define AHIP_LU_TILE_WAVE 32
+int ahip_lu_tile_max(void);
+int ahip_lu_tile(int dtype, int64_t batch, int64_t n, const void* A, int64_t a_bs, int64_t a_rs, int64_t a_cs,
+                 void* inv, void* det, void* info, void* stream);
 /* ---- K19: Householder QR ----------------------------------------------------------------------
  * the kernels under tensor/nlinalg.py:403 QRFull (np.linalg.qr: LAPACK geqrf + orgqr).  As for K18
  * only what is not a product: the caller owns the panel loop and applies a block reflector
